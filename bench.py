@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- measures BASELINE.json's metric on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ei|train|densenet|all]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py --full [--gpus N] [--steps K] [--warmup W] [--workload ei|fit|train|densenet|search|search3|all]
+
+A plain run measures the headline figure only: it sets up the EI workload below,
+warms up, times K steps, writes the last step's outputs if --dump-outputs is
+given, and prints the result line.  Everything else -- the rocprofv3 traffic
+passes, the kernel-alone and prepare timings and the roofline of the EI leg, the
+GP-refit / training / DenseNet / search legs, the CPU baselines, the 8-GPU
+projection and the per-leg summary -- runs under --full.
 
 N=1 workload = BASELINE configs[1]: the GP/EI "ask" step, 200 observations,
 10-dim space, 1M candidates, fp64.  One *step* = one full acquisition pass of the
@@ -189,7 +197,7 @@ def live_pmc(train_trials):
         # stats) over the bench's own EI leg in a child process (the same sustained
         # launches: a short probe runs at a higher clock -- 0.96 vs 1.31 ms measured);
         # the roofline's HIP-event time is measured in this process beside it
-        calls, avg_ns = kernel_trace_pass([os.path.join(ROOT, "bench.py"), "--workload", "ei", "--no-pmc",
+        calls, avg_ns = kernel_trace_pass([os.path.join(ROOT, "bench.py"), "--full", "--workload", "ei", "--no-pmc",
                                            "--no-cpu-baseline"], lambda k: "gp_score_kernel" in k, timeout=300)
         out["ei"]["rocprof_calls"], out["ei"]["rocprof_avg_ns"] = calls, avg_ns
     except Exception as e:  # noqa: BLE001 -- reported, the bench line carries traffic null
@@ -310,8 +318,9 @@ def bench_ei(args, torch, dist, ws, rank, dev):
         dist.barrier()
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
+    out = None
     for _ in range(args.steps):
-        step()
+        out = step()
     torch.cuda.synchronize(dev)
     if ws > 1:
         dist.barrier()
@@ -320,6 +329,29 @@ def bench_ei(args, torch, dist, ws, rank, dev):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0 and out is not None:
+        dump_ei_outputs(args.dump_outputs, out)
+
+    res = {
+        "metric": "EI candidates/sec (GP/EI ask step, N=200 obs, D=10, fp64)",
+        "value": ws * m * args.steps / dt,
+        "unit": "candidates/s",
+        "n_gpus": ws,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (SURVEY §8d recipe: X~U[0,1]^{200x10}, y=sin(Xw)+0.1eps; candidates~U[0,1]^{1Mx10})",
+        "config": {"workload": "BASELINE configs[1]: GP/EI ask step, 200 observations, 10-dim, "
+                               f"{m} candidates per GPU, top-{k} (skopt argsort[:n_restarts])",
+                   "n_obs": n, "dims": d, "candidates_per_gpu": m,
+                   "parallelism": f"candidates sharded, {ws} GPU(s), all-gather of (value,index)"},
+    }
+    if not args.full:
+        return res
 
     # dominant kernel alone (k=0: no top-k merge), HIP events on its stream
     stream = torch.cuda.current_stream(dev)
@@ -346,28 +378,11 @@ def bench_ei(args, torch, dist, ws, rank, dev):
     flops = ei_flops_per_candidate(n, d) * m
     algo_bytes = ei_bytes_per_candidate(d) * m
     achieved = flops / t_kernel / 1e12
-    value = ws * m * args.steps / dt
-    res = {
-        "metric": "EI candidates/sec (GP/EI ask step, N=200 obs, D=10, fp64)",
-        "value": value,
-        "unit": "candidates/s",
-        "n_gpus": ws,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3,
+    res.update({
         "ask_step_ms": {"prepare": t_prep * 1e3, "score": dt / args.steps * 1e3,
                         "total": (t_prep + dt / args.steps) * 1e3,
                         "note": "prepare = DeviceGP construction (H2D of X, y + mpo_gp_prepare), once per "
                                 "fitted model; value / ms_per_step time the scoring pass alone"},
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (SURVEY §8d recipe: X~U[0,1]^{200x10}, y=sin(Xw)+0.1eps; candidates~U[0,1]^{1Mx10})",
-        "config": {"workload": "BASELINE configs[1]: GP/EI ask step, 200 observations, 10-dim, "
-                               f"{m} candidates per GPU, top-{k} (skopt argsort[:n_restarts])",
-                   "n_obs": n, "dims": d, "candidates_per_gpu": m,
-                   "parallelism": f"candidates sharded, {ws} GPU(s), all-gather of (value,index)"},
         "roofline": {"kernel": "gp_score_kernel (one acquisition pass, finish fused)", "bound": "mfma",
                      "achieved": achieved,
                      "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / FP64_PEAK_TFLOPS,
@@ -379,8 +394,19 @@ def bench_ei(args, torch, dist, ws, rank, dev):
                      "algorithmic_flops_per_launch": flops,
                      "algorithmic_hbm_bytes_per_launch": algo_bytes,
                      "algorithmic_hbm_gbs": algo_bytes / t_kernel / 1e9},
-    }
+    })
     return res
+
+
+def dump_ei_outputs(path, out):
+    """--dump-outputs: what the last timed ``DeviceGP.score`` call returned (posterior
+    mean and std and the EI value of every candidate, the top-k indices and values),
+    one float64 ``<name>.npy`` each."""
+    os.makedirs(path, exist_ok=True)
+    idx, val = out["topk"]["EI"]
+    arrays = {"mu": out["mu"], "sd": out["sd"], "ei_values": out["values"]["EI"], "topk_index": idx, "topk_value": val}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float64))
 
 
 def _rocprof_ms(args):
@@ -1177,8 +1203,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--workload", default="all",
-                    choices=["ei", "fit", "train", "densenet", "search", "search3", "all"])
+    ap.add_argument("--full", action="store_true",
+                    help="every leg and side measurement (traffic passes, roofline, other workloads, CPU baselines, "
+                         "projection); a plain run times the headline EI steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed EI step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--workload", default=None,
+                    choices=["ei", "fit", "train", "densenet", "search", "search3", "all"],
+                    help="with --full: the legs to run (default all); a plain run is the ei leg")
     ap.add_argument("--search-args", nargs="*", default=None,
                     help="extra search CLI flags appended to configs[0]'s (e.g. --n-samples 6000)")
     ap.add_argument("--search3-args", nargs="*", default=None,
@@ -1192,12 +1224,19 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 traffic passes")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and args.workload not in (None, "ei"):
+        ap.error(f"--workload {args.workload} is measured under --full")
+    args.workload = args.workload or ("all" if args.full else "ei")
+    if args.dump_outputs and args.workload not in ("ei", "all"):
+        ap.error("--dump-outputs writes the EI leg's outputs: use --workload ei or all")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch_distributed(args.gpus))
     ws, rank, local = dist_env()
     args.pmc = None
-    if ws == 1 and not args.no_pmc and args.workload in ("ei", "train", "densenet", "all") and shutil.which("rocprofv3"):
+    if args.full and ws == 1 and not args.no_pmc and args.workload in ("ei", "train", "densenet", "all") and shutil.which("rocprofv3"):
         t0 = time.perf_counter()
         args.pmc = live_pmc(args.train_trials)      # child processes, before this one touches the GPU
         args.pmc["wall_s"] = time.perf_counter() - t0
@@ -1227,7 +1266,7 @@ def main():
     srch = bench_search(args, torch, dist, ws, rank, dev) if args.workload in ("search", "all") else None
     srch3 = bench_search_gp(args, torch, dist, ws, rank, dev) if args.workload in ("search3", "all") else None
     if rank == 0:
-        cpu = ws == 1 and not args.no_cpu_baseline
+        cpu = args.full and ws == 1 and not args.no_cpu_baseline
         if srch is not None:
             if cpu:
                 srch["cpu_baseline"] = cpu_baseline_search(srch)
@@ -1252,7 +1291,8 @@ def main():
         if dn is not None:
             dn["cpu_baseline"] = cpu_baseline_densenet() if cpu else None
         if res is not None:
-            res["cpu_baseline"] = cpu_baseline_ei() if cpu else None
+            if args.full:
+                res["cpu_baseline"] = cpu_baseline_ei() if cpu else None
             if fit is not None:
                 res["gp_fit"] = fit
             if train is not None:
@@ -1265,7 +1305,8 @@ def main():
                 res["search_gp"] = srch3
         else:
             res = next(r for r in (train, dn, srch, srch3, fit) if r is not None)
-        res["summary"] = summary(res)      # last key: a stored tail of the line keeps every leg
+        if args.full:
+            res["summary"] = summary(res)  # last key: a stored tail of the line keeps every leg
         print(json.dumps(res), flush=True)
     if ws > 1:
         dist.barrier()

@@ -1,6 +1,9 @@
 #!/bin/bash
+# The whole benchmark (every leg: --full); BENCH_ARGS adds flags.  Output under $OUT.
 set -o pipefail
-cd "${GRAFT_REPO_ROOT:-/root/repo}"
-mkdir -p gpurun_out
+ROOT="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
+OUT="${OUT:-$ROOT/bench_out}"
+cd "$ROOT"
+mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 400 python -u bench.py ${BENCH_ARGS} > gpurun_out/bench.json 2> gpurun_out/bench.err && cat gpurun_out/bench.json
+timeout -k 10 400 python -u bench.py --full ${BENCH_ARGS} > "$OUT/bench.json" 2> "$OUT/bench.err" && cat "$OUT/bench.json"

@@ -1,11 +1,13 @@
 #!/bin/bash
 # one SQ counter pass over the DenseNet bench leg; per-kernel-family sums
+ROOT="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
+export OUT="${OUT:-$ROOT/bench_out}"
 cd /tmp && rm -rf /tmp/dpmc && timeout -s KILL 200 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES GRBM_GUI_ACTIVE \
-    -d /tmp/dpmc -o pmc --output-format csv -- python "$GRAFT_REPO_ROOT/bench.py" --workload densenet --no-cpu-baseline --no-pmc --train-steps 2 > /tmp/dpmc.log 2>&1 || { tail -5 /tmp/dpmc.log; exit 1; }
-mkdir -p "$GRAFT_REPO_ROOT/gpurun_out/dnpmc" && cp $(find /tmp/dpmc -name "*counter_collection.csv") "$GRAFT_REPO_ROOT/gpurun_out/dnpmc/"
+    -d /tmp/dpmc -o pmc --output-format csv -- python "$ROOT/bench.py" --full --workload densenet --no-cpu-baseline --no-pmc --train-steps 2 > /tmp/dpmc.log 2>&1 || { tail -5 /tmp/dpmc.log; exit 1; }
+mkdir -p "$OUT/dnpmc" && cp $(find /tmp/dpmc -name "*counter_collection.csv") "$OUT/dnpmc/"
 python3 - <<'PY'
 import csv, glob, os, re, collections
-f = glob.glob(os.environ["GRAFT_REPO_ROOT"] + "/gpurun_out/dnpmc/*counter_collection.csv")[0]
+f = glob.glob(os.environ["OUT"] + "/dnpmc/*counter_collection.csv")[0]
 agg = collections.defaultdict(lambda: collections.defaultdict(float))
 for r in csv.DictReader(open(f)):
     m = re.search(r"::(dn_\w+)", r["Kernel_Name"])

@@ -1,11 +1,13 @@
 #!/bin/bash
 # DenseNet leg alone under rocprofv3 --kernel-trace --stats; per-family summary
+ROOT="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
+export OUT="${OUT:-$ROOT/bench_out}"
 cd /tmp && rm -rf /tmp/dnp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d /tmp/dnp -o dn --output-format csv -- \
-    python "$GRAFT_REPO_ROOT/bench.py" --workload densenet --no-cpu-baseline --no-pmc > /tmp/dnp.log 2>&1 || { tail -5 /tmp/dnp.log; exit 1; }
-mkdir -p "$GRAFT_REPO_ROOT/gpurun_out/dnprof" && cp $(find /tmp/dnp -name "*kernel_stats.csv") "$GRAFT_REPO_ROOT/gpurun_out/dnprof/"
+    python "$ROOT/bench.py" --full --workload densenet --no-cpu-baseline --no-pmc > /tmp/dnp.log 2>&1 || { tail -5 /tmp/dnp.log; exit 1; }
+mkdir -p "$OUT/dnprof" && cp $(find /tmp/dnp -name "*kernel_stats.csv") "$OUT/dnprof/"
 python3 - <<'PY'
 import csv, glob, re, os
-f = glob.glob(os.environ["GRAFT_REPO_ROOT"] + "/gpurun_out/dnprof/*kernel_stats.csv")[0]
+f = glob.glob(os.environ["OUT"] + "/dnprof/*kernel_stats.csv")[0]
 rows = [r for r in csv.DictReader(open(f)) if "::dn_" in r["Name"]]
 tot = sum(float(r["TotalDurationNs"]) for r in rows)
 agg = {}

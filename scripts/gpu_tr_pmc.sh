@@ -1,11 +1,13 @@
 #!/bin/bash
 # one SQ counter pass over the MNIST training bench leg; per-kernel (with template args) sums
+ROOT="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
+export OUT="${OUT:-$ROOT/bench_out}"
 cd /tmp && rm -rf /tmp/tpmc && timeout -s KILL 200 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES GRBM_GUI_ACTIVE \
-    -d /tmp/tpmc -o pmc --output-format csv -- python "$GRAFT_REPO_ROOT/bench.py" --workload train --no-cpu-baseline --no-pmc --train-steps 2 > /tmp/tpmc.log 2>&1 || { tail -5 /tmp/tpmc.log; exit 1; }
-mkdir -p "$GRAFT_REPO_ROOT/gpurun_out/trpmc" && cp $(find /tmp/tpmc -name "*counter_collection.csv") "$GRAFT_REPO_ROOT/gpurun_out/trpmc/"
+    -d /tmp/tpmc -o pmc --output-format csv -- python "$ROOT/bench.py" --full --workload train --no-cpu-baseline --no-pmc --train-steps 2 > /tmp/tpmc.log 2>&1 || { tail -5 /tmp/tpmc.log; exit 1; }
+mkdir -p "$OUT/trpmc" && cp $(find /tmp/tpmc -name "*counter_collection.csv") "$OUT/trpmc/"
 python3 - <<'PY'
 import csv, glob, os, re, collections
-f = glob.glob(os.environ["GRAFT_REPO_ROOT"] + "/gpurun_out/trpmc/*counter_collection.csv")[0]
+f = glob.glob(os.environ["OUT"] + "/trpmc/*counter_collection.csv")[0]
 agg = collections.defaultdict(lambda: collections.defaultdict(float))
 for r in csv.DictReader(open(f)):
     m = re.search(r"::(\w+(<[^>]*>)?)\(", r["Kernel_Name"])
