@@ -92,7 +92,7 @@ int mpo_chol_f64(double* A, int n, int lda, int32_t* info, void* stream);
 int mpo_trsm_f64(const double* L, int n, int lda, double* B, int nrhs, int ldb,
                  int trans, void* stream);
 
-/* Workspace bytes for mpo_gp_prepare. */
+/* Workspace bytes for mpo_gp_prepare; 0 for n > 2048, d > 32 or bad arguments. */
 size_t mpo_gp_prepare_ws_bytes(int n, int d);
 
 /* Build a GP posterior from observations and fitted hyper-parameters:
@@ -110,6 +110,13 @@ size_t mpo_gp_prepare_ws_bytes(int n, int d);
  * takes the direct differences.  tests/test_gp_gpu.py checks the expanded path
  * against the exact posterior at 1e-9 on the fixtures and on a small-noise,
  * near-duplicate-observation problem.  MPO_GP_DIST=0 disables it.
+ * Two scoring paths serve a prepared model (mpo_gp_score_path): "resident" while the
+ * K* tile of 16 candidates x np16 observations fits the 160 KiB LDS (np16 <= 1248 at
+ * dp = 4, 1232 at dp = 8 / 12, 1216 at dp = 32), "streamed" past it, up to n = 2048;
+ * n > 2048 returns MPO_ENOTSUP.  A streamed model always takes the direct distance
+ * (xb = NULL, no self-check).  MPO_GP_SCORE=streamed forces the streamed path at any n
+ * (resident or unset: the automatic choice); MPO_GP_PANEL=<rows> (a multiple of 16,
+ * >= 16, else MPO_EINVAL) sets its panel height.  Both are read here and at score time.
  * X [n][d], y_norm [n], ls [d]: device.  `model` (host struct) receives
  * device pointers into `ws`, which must stay alive while the model is used.
  * Replaces GaussianProcessRegressor.fit's tail (sklearn _gpr.py:345-365) and
@@ -149,8 +156,16 @@ int mpo_gp_lml_grad_host(const double* X, const double* y_norm, int n, int d,
                          const double* theta_host, int batch, double* out_host,
                          void* dev_io, size_t io_bytes, void* ws, size_t ws_bytes, void* stream);
 
-/* Workspace bytes for mpo_gp_acq_score over m candidates. */
+/* Workspace bytes for mpo_gp_acq_score over m candidates; 0 for a model with
+ * n > 2048, k > MPO_TOPK_MAX or bad arguments.  A streamed model adds its
+ * workgroups' partial rows (at most 48 MiB; 26 MiB at n = 2048 with the default panel). */
 size_t mpo_gp_score_ws_bytes(const MpoGpModel* model, int64_t m, int k);
+
+/* Which scoring kernel mpo_gp_acq_score / mpo_gp_ei_score run for this model under
+ * the current MPO_GP_SCORE / MPO_GP_PANEL: 0 resident, 1 streamed, negative
+ * (-MPO_ENOTSUP: n > 2048; -MPO_EINVAL: malformed model or panel value) when the
+ * model cannot be scored.  Host arithmetic only: reads n, dp and np16. */
+int mpo_gp_score_path(const MpoGpModel* model);
 
 /* Score m candidates (transformed space, [m][d] device) under the posterior:
  *   mu, sd           : posterior mean / std (skopt predict(return_std=True));
@@ -159,6 +174,11 @@ size_t mpo_gp_score_ws_bytes(const MpoGpModel* model, int64_t m, int k);
  *   topk_idx/val[a*k + r] : the k smallest values of acquisition a, ties to the
  *                      lowest index (np.argsort(values)[:k] / np.argmin).
  * Any of mu, sd, vals may be NULL (not written).  topk arrays are device.
+ * Resident path: K* of a 16-candidate tile stays in the LDS for the whole triangular
+ * product.  Streamed path (models past the LDS limit, n <= 2048): K* is built one
+ * panel of observations at a time; the later panels' partial rows of L^-1 K*^T wait
+ * in the workspace.  Same posterior, same top-k and tie rules, same NULL-output
+ * rules; no allocation, no host synchronisation, capturable in a graph.
  * Replaces skopt _gaussian_acquisition + gaussian_ei/pi/lcb over the
  * n_points candidate sample, and the argsort/argmin that picks L-BFGS starts. */
 int mpo_gp_acq_score(const MpoGpModel* model, const double* cand, int64_t m,

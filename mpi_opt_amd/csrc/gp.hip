@@ -17,6 +17,9 @@
 //                                          only the lower-triangular k-steps,
 //                                          ||V_row||^2 accumulated in registers
 //                          phase 3:        sd, mu, -EI/-PI/LCB, block top-k
+//   gp_score_streamed_kernel  the same posterior for models whose K* tile does not
+//                        fit the LDS (n <= 2048): K* one panel of observations at a
+//                        time, later panels' partial rows in the score workspace
 //   topk_merge_kernel    workgroup top-k lists -> global top-k (lowest index ties)
 //
 // Why the triangular form: skopt evaluates sd^2 = amp - k^T K_inv k with an
@@ -432,6 +435,9 @@ struct ScoreArgs {
     long long* part_idx;  // [nparts][3][k]
     double* part_val;
     double* mq;           // [m][2] raw (mu_n, q) rows (FIN = 0 only: the prepare-time self-check)
+    // streamed path only (gp_score_streamed_kernel)
+    int panel;            // observation rows per K* panel (a multiple of 16)
+    double* part;         // [grid][T - panel/16][256] partial rows of the later panels' column tiles
 };
 
 // One wave, 64 candidates (lane = candidate; invalid lanes contribute nothing): the
@@ -787,6 +793,216 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
 #undef MPO_LOAD_TILE
 }
 
+// ---------------------------------------------------------------------------
+// Streamed scoring: the same posterior for models whose K* tile (16 candidates x
+// np16 observations) does not fit the LDS.  The observation axis is cut into
+// panels of a.panel rows (PT = panel / 16 column tiles); with k = [k_0; k_1; ...]
+// and W = L^-1 block lower-triangular, v_I = sum_{J <= I} W[I,J] k_J.  Per
+// candidate tile the workgroup walks the panels J in order:
+//   phase 1 (VALU)  K*[16][panel J] (direct distance form) into the LDS, mu partials
+//   phase 2 (MFMA)  for every column tile jt at or below panel J (dealt to the 4
+//                   waves by jt mod 4, rotated by workgroup), the k-step groups of
+//                   panel J only: groups t0..jt inside the panel (the triangular
+//                   part), all of t0..t1-1 for the later panels (rectangular).  A
+//                   tile inside panel J is complete: its ||V_row||^2 joins sq.  A
+//                   later tile's partial row u = W[jt, 0..J] k goes to this
+//                   workgroup's slice of the score workspace and seeds the
+//                   accumulator when the next panel reaches the tile.
+// The slice is written and read back by the same lane of the same wave (no
+// barrier, no atomics); it holds (T - PT) x 2 KiB and stays in L2.  Registers
+// cannot hold it in general (n = 2048 at the largest panel: 13 later tiles per wave =
+// 104 VGPRs per lane, with static indexing only; a forced 16-row panel: 127 tiles).  W is read
+// from the resident path's fragment stream: tile jt's groups lie back to back at
+// tile_off[jt] (wmeta), so no second packing exists.  Worst-case growth of the
+// score workspace: n = 2048, dp = 12, panel 1232 -> 51 tiles x 2 KiB x 256
+// workgroups = 25.5 MiB (26 MiB at dp = 32, panel 1216; streamed_grid_cap keeps any
+// forced panel under 48 MiB).
+// The finish is the resident kernel's: own (mu_n, q) rows, score_finish_group, one
+// top-k list per wave.
+template <int DP, int D>
+__global__ __launch_bounds__(256) void gp_score_streamed_kernel(ScoreArgs a) {
+    constexpr int BM = kBM;
+    constexpr int S = 16;            // i-slots per block in phase 1 (4 per wave)
+    static_assert(4 * 3 * MPO_TOPK_MAX * 16 <= 16 * kBM * 8, "the finish's top-k lists live in the smallest panel");
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int T = a.T, PT = a.panel >> 4;
+    double* kc = smem;                          // [panel/4][64]: local k-step ks at kc[ks*64]
+    double* cs = kc + (size_t)a.panel * BM;     // [BM][DP]
+    double* red = cs + BM * DP;                 // [S][BM] (mu) + [4][BM] (q)
+    int32_t* toff = reinterpret_cast<int32_t*>(red + (S + 4) * BM);   // [T] group offset of tile jt in wfrag
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const long long ntiles = (a.m + BM - 1) / BM;
+    const int row = lane & 15;
+    const int slot = wave * 4 + (lane >> 4);
+    double* part = a.part + (size_t)blockIdx.x * (size_t)(T > PT ? T - PT : 0) * 256 + lane;
+
+    for (int e = tid; e < T; e += 256) toff[e] = a.wmeta[4 * (T + 4) + e];
+
+    for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const long long m0 = tile * BM;
+        // ---- phase 0: candidate tile / ls -> LDS
+        for (int e = tid; e < BM * DP; e += 256) {
+            const int r = e / DP, c = e % DP;
+            const long long gm = m0 + r;
+            cs[e] = (gm < a.m && c < a.d) ? __builtin_nontemporal_load(a.cand + gm * a.d + c) / a.ls[c] : 0.0;
+        }
+        __syncthreads();
+        double c[D];
+#pragma unroll
+        for (int q = 0; q < D; ++q) c[q] = cs[row * DP + q];
+        double mu_acc = 0.0;
+        double sq[4] = {0.0, 0.0, 0.0, 0.0};
+
+        for (int t0 = 0; t0 < T; t0 += PT) {
+            const int t1 = min(T, t0 + PT);
+            // ---- phase 1: K*[row][r0..r1) in A-fragment order (panel-local k-steps)
+            for (int i = t0 * 16 + slot; i < t1 * 16; i += S) {
+                const double* xr = a.xs + (size_t)i * DP;
+                double r2 = kR2Floor;
+#pragma unroll
+                for (int q = 0; q < D; ++q) {
+                    const double t = c[q] - xr[q];
+                    r2 = fma(t, t, r2);
+                }
+                const double kv = matern52_unit(r2);   // amp folded into mu and q below
+                mu_acc = fma(kv, a.alpha[i], mu_acc);
+                const int li = i - t0 * 16;
+                kc[(size_t)(li >> 2) * 64 + row + (li & 3) * 16] = kv;
+            }
+            __syncthreads();
+            // ---- phase 2: this panel's k-steps of every column tile at or below it
+            for (int jt = t0 + ((wave - t0 - (int)blockIdx.x) & 3); jt < T; jt += 4) {
+                const int ng = min(jt, t1 - 1) - t0 + 1;   // groups of 4 k-steps
+                f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
+                double* pr = part + (size_t)(jt - PT) * 256;   // used only when jt >= PT
+                if (t0 > 0) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc0[r] = pr[r * 64];
+                }
+                const double* bp = a.wfrag + ((size_t)__builtin_amdgcn_readfirstlane(toff[jt]) + t0) * 256 + lane;
+                const double* ap = kc + lane;
+                // B fragments through a three-group register ring filled by asm loads with
+                // explicit vmcnt waits, as in gp_score_kernel (compiler-visible loads
+                // were drained every iteration: the compiler rotated them to the loop
+                // top and waited vmcnt(0) at its end).  Loads return in order, so
+                // vmcnt(8) leaves only the two younger groups in flight.  The ring
+                // lives inside one column tile and is drained at its end; loads past
+                // the tile's last group re-read that group, so nothing outside the
+                // tile's own fragments is touched.
+#define MPO_ST_LD(B, G)                                                                        \
+                {                                                                              \
+                    const double* p = bp + (size_t)min((G), ng - 1) * 256;                     \
+                    asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(B[0]) : "v"(p) : "memory");              \
+                    asm volatile("global_load_dwordx2 %0, %1, off offset:512" : "=v"(B[1]) : "v"(p) : "memory");   \
+                    asm volatile("global_load_dwordx2 %0, %1, off offset:1024" : "=v"(B[2]) : "v"(p) : "memory");  \
+                    asm volatile("global_load_dwordx2 %0, %1, off offset:1536" : "=v"(B[3]) : "v"(p) : "memory");  \
+                }
+#define MPO_ST_GROUP(B, G)                                                                     \
+                {                                                                              \
+                    asm volatile("s_waitcnt vmcnt(8)" : "+v"(B[0]), "+v"(B[1]), "+v"(B[2]), "+v"(B[3]));  \
+                    const double* q = ap + (size_t)(G) * 256;                                  \
+                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[0], B[0], acc0, 0, 0, 0);    \
+                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[64], B[1], acc1, 0, 0, 0);   \
+                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[128], B[2], acc0, 0, 0, 0);  \
+                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[192], B[3], acc1, 0, 0, 0);  \
+                    MPO_ST_LD(B, (G) + 3)                                                      \
+                }
+                // The ring loop runs whole rotations only, without a branch in its body
+                // (a body with exits made the compiler copy ring registers between
+                // blocks while their loads were in flight); the ng % 3 groups left over
+                // go first, through ordinary loads, under the ring's initial fill.
+                const int rem = ng % 3;
+                double b0[4], b1[4], b2[4];
+                MPO_ST_LD(b0, rem)
+                MPO_ST_LD(b1, rem + 1)
+                MPO_ST_LD(b2, rem + 2)
+                for (int g = 0; g < rem; ++g) {
+                    const double* p = bp + (size_t)g * 256;
+                    const double* q = ap + (size_t)g * 256;
+                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[0], p[0], acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[64], p[64], acc1, 0, 0, 0);
+                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[128], p[128], acc0, 0, 0, 0);
+                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[192], p[192], acc1, 0, 0, 0);
+                }
+                for (int g = rem; g < ng; g += 3) {
+                    MPO_ST_GROUP(b0, g)
+                    MPO_ST_GROUP(b1, g + 1)
+                    MPO_ST_GROUP(b2, g + 2)
+                }
+                asm volatile("s_waitcnt vmcnt(0)" : "+v"(b0[0]), "+v"(b0[1]), "+v"(b0[2]), "+v"(b0[3]), "+v"(b1[0]),
+                             "+v"(b1[1]), "+v"(b1[2]), "+v"(b1[3]), "+v"(b2[0]), "+v"(b2[1]), "+v"(b2[2]), "+v"(b2[3]));
+#undef MPO_ST_GROUP
+#undef MPO_ST_LD
+                if (jt < t1) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const double v = acc0[r] + acc1[r];
+                        sq[r] = fma(v, v, sq[r]);
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) pr[r * 64] = acc0[r] + acc1[r];
+                }
+            }
+            __syncthreads();   // the panel's K* is rewritten by the next phase 1
+        }
+
+        // ---- (mu_n, q) row: mu over the 16 slots, q over the 4 waves' column sums
+        // (f64 C/D map: col = lane & 15, row = (lane >> 4) + 4 r)
+        red[slot * BM + row] = mu_acc;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            double v = sq[r];
+            v += __shfl_xor(v, 1);
+            v += __shfl_xor(v, 2);
+            v += __shfl_xor(v, 4);
+            v += __shfl_xor(v, 8);
+            if ((lane & 15) == 0) red[(S + wave) * BM + (lane >> 4) + 4 * r] = v;
+        }
+        __syncthreads();
+        if (wave == 0 && lane < BM && m0 + lane < a.m) {
+            double mu_n = 0.0;
+#pragma unroll
+            for (int s = 0; s < S; ++s) mu_n += red[s * BM + lane];
+            mu_n *= a.amp;
+            const double q = (red[(S + 0) * BM + lane] + red[(S + 1) * BM + lane] + red[(S + 2) * BM + lane] +
+                              red[(S + 3) * BM + lane]) * (a.amp * a.amp);
+            *reinterpret_cast<double2*>(a.mq + 2 * (m0 + lane)) = double2{mu_n, q};
+        }
+        // red and cs are next written behind the next tile's barriers
+    }
+
+    // ---- finish: as gp_score_kernel<.., FIN = 1>
+    __syncthreads();
+    const ScoreArgs* ap = (const ScoreArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ap));
+    const ScoreArgs& f = *ap;
+    double* tk_val = kc + wave * 3 * MPO_TOPK_MAX;
+    long long* tk_idx = reinterpret_cast<long long*>(kc + 4 * 3 * MPO_TOPK_MAX) + wave * 3 * MPO_TOPK_MAX;
+    if (lane < 3 * MPO_TOPK_MAX) {
+        tk_val[lane] = __builtin_huge_val();
+        tk_idx[lane] = 0x7fffffffffffffffLL;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const long long ntl = ((f.m + BM - 1) / BM - blockIdx.x + gridDim.x - 1) / gridDim.x;   // this workgroup's tiles
+    for (long long c0 = (long long)wave * 64; c0 < ntl * BM; c0 += 256) {
+        const long long cl = c0 + lane;
+        const long long gm = (blockIdx.x + (cl >> 4) * (long long)gridDim.x) * BM + (cl & 15);
+        const bool valid = cl < ntl * BM && gm < f.m;
+        double2 v = {0.0, 0.0};
+        if (valid) v = *reinterpret_cast<const double2*>(f.mq + 2 * gm);
+        score_finish_group(f, valid, gm, v.x, v.y, lane, tk_val, tk_idx);
+    }
+    if (f.k > 0 && lane < 3 * f.k) {
+        const int acq = lane / f.k, r = lane - acq * f.k;
+        const size_t part_i = (size_t)blockIdx.x * 4 + wave;
+        f.part_val[(part_i * 3 + acq) * f.k + r] = tk_val[acq * MPO_TOPK_MAX + r];
+        f.part_idx[(part_i * 3 + acq) * f.k + r] = tk_idx[acq * MPO_TOPK_MAX + r];
+    }
+}
+
 // Merge per-block top-k lists.  grid = (G, 3): block g of acquisition y merges
 // the partial lists [g*chunk, min((g+1)*chunk, nparts)) and writes one list.
 // Stage 1 writes the partial layout [(g*3 + acq)*k + r]; the final stage (G = 1)
@@ -891,6 +1107,51 @@ size_t score_lds_bytes(int dp, int np16) {
 
 bool score_fits(int dp, int np16) { return score_lds_bytes(dp, np16) <= kMaxLds; }
 
+// ---- streamed path (gp_score_streamed_kernel): models past score_fits, n <= kScoreMaxN
+constexpr int kScoreMaxN = 2048;                  // = kFitMaxN of the refit (gp_fit.hip)
+constexpr size_t kStreamPartCap = (size_t)48 << 20;   // bytes of partial rows per scoring call
+
+// one K* panel, cs, red (mu slots + q) | tile offsets
+size_t streamed_lds_bytes(int dp, int np16, int panel) {
+    return ((size_t)panel * kBM + (size_t)kBM * dp + 20 * kBM) * sizeof(double) + (size_t)(np16 / 16) * sizeof(int32_t);
+}
+
+// Which scoring kernel serves a model: 0 resident, 1 streamed (*panel = its panel
+// rows), -MPO_ENOTSUP past kScoreMaxN, -MPO_EINVAL for a malformed model or switch.
+// Host arithmetic only.  MPO_GP_SCORE=streamed forces the streamed kernel at any n
+// ("resident" or unset: resident whenever it fits); MPO_GP_PANEL=<rows> (a multiple
+// of 16, >= 16) sets the panel, clamped to the largest one that fits the LDS.
+int score_plan(int n, int dp, int np16, int* panel) {
+    if (n <= 0 || np16 < n || np16 - n >= 16 || (np16 & 15) ||
+        !(dp == 4 || dp == 8 || dp == 12 || dp == 16 || dp == 32))
+        return -MPO_EINVAL;
+    if (n > kScoreMaxN) return -MPO_ENOTSUP;
+    const char* e = getenv("MPO_GP_SCORE");
+    const bool forced = e && std::string(e) == "streamed";
+    if (!forced && score_fits(dp, np16)) return 0;
+    int p = np16;
+    while (p > 16 && streamed_lds_bytes(dp, np16, p) > kMaxLds) p -= 16;
+    if (const char* pe = getenv("MPO_GP_PANEL"); pe && *pe) {
+        char* end = nullptr;
+        const long v = strtol(pe, &end, 10);
+        if (*end || v < 16 || v % 16) return -MPO_EINVAL;
+        p = (int)std::min<long>(p, v);
+    }
+    if (panel) *panel = p;
+    return 1;
+}
+
+// Streamed grid bound, from host arithmetic only (the workspace query runs without a
+// device): the resident capacity at this LDS size on 256 CUs, lowered until the
+// partial rows of all workgroups fit kStreamPartCap.
+int streamed_grid_cap(int dp, int np16, int panel) {
+    const int per_cu = (int)std::min<size_t>(8, kMaxLds / streamed_lds_bytes(dp, np16, panel));
+    int cap = std::min(kScoreGridCap, std::max(1, per_cu) * 256);
+    const size_t slice = (size_t)(np16 - panel) * kBM * sizeof(double);
+    if (slice) cap = (int)std::min<size_t>(cap, std::max<size_t>(1, kStreamPartCap / slice));
+    return cap;
+}
+
 // grid = the device's resident capacity for this variant (tiles are looped over);
 // *grid_out receives it (FIN: one top-k list per workgroup)
 template <int DP, int D, int OCC, int MD, int FIN>
@@ -972,6 +1233,42 @@ hipError_t launch_score_dp(int dp, int d, const ScoreArgs& a, int nblocks, size_
                                 : launch_score_occ<12, 12>(a, nblocks, lds, s, fin, grid_out);
         case 16: return launch_score_occ<16, 16>(a, nblocks, lds, s, fin, grid_out);
         case 32: return launch_score_occ<32, 32>(a, nblocks, lds, s, fin, grid_out);
+    }
+    return hipErrorInvalidValue;
+}
+
+// streamed kernel: grid = min(tiles, streamed_grid_cap (the workspace is sized from
+// it), the device's resident capacity).  The B ring's asm loads are invisible to the
+// compiler: a variant that spills is refused, as in launch_score.
+template <int DP, int D>
+hipError_t launch_streamed(const ScoreArgs& a, int ntiles, hipStream_t s, int* grid_out) {
+    auto kern = gp_score_streamed_kernel<DP, D>;
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern)) != hipSuccess || fa.localSizeBytes != 0)
+        return hipErrorInvalidDeviceFunction;
+    const size_t lds = streamed_lds_bytes(DP, a.np16, a.panel);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)lds);
+    int dev = 0, cus = 0, per_cu = 0;
+    (void)hipGetDevice(&dev);
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 256, lds);
+    const int grid = std::max(1, std::min(std::min(ntiles, streamed_grid_cap(DP, a.np16, a.panel)),
+                                          std::max(1, per_cu) * std::max(1, cus)));
+    if (grid_out) *grid_out = grid;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_streamed_dp(int dp, int d, const ScoreArgs& a, int ntiles, hipStream_t s, int* grid_out) {
+    switch (dp) {
+        case 4: return launch_streamed<4, 4>(a, ntiles, s, grid_out);
+        case 8: return d == 5 ? launch_streamed<8, 5>(a, ntiles, s, grid_out)
+                              : launch_streamed<8, 8>(a, ntiles, s, grid_out);
+        case 12: return d == 10 ? launch_streamed<12, 10>(a, ntiles, s, grid_out)
+                                : launch_streamed<12, 12>(a, ntiles, s, grid_out);
+        case 16: return launch_streamed<16, 16>(a, ntiles, s, grid_out);
+        case 32: return launch_streamed<32, 32>(a, ntiles, s, grid_out);
     }
     return hipErrorInvalidValue;
 }
@@ -1418,13 +1715,20 @@ struct ScoreWs {
     long long* tail_idx;
     double* tail_val;
     double* mq;
+    double* part;   // streamed path: the workgroups' partial-row slices (part_elems doubles)
 };
 
 // top-k lists: 4 per workgroup (one per wave); a workgroup has at least one tile
 // and the grid never exceeds kScoreGridCap (tiles are looped over)
 inline int64_t score_nparts(int64_t m) { return 4 * std::min<int64_t>((m + kBM - 1) / kBM, kScoreGridCap); }
 
-inline ScoreWs carve_score_ws(void* ws, int64_t m, int k, size_t* used) {
+// doubles of partial rows a streamed scoring call over m candidates needs
+inline size_t streamed_part_elems(int dp, int np16, int panel, int64_t m) {
+    const int64_t grid = std::min<int64_t>((m + kBM - 1) / kBM, streamed_grid_cap(dp, np16, panel));
+    return (size_t)grid * (size_t)(np16 - panel) * kBM;
+}
+
+inline ScoreWs carve_score_ws(void* ws, int64_t m, int k, size_t* used, size_t part_elems = 0) {
     const int64_t nparts = score_nparts(m);
     const int kk = std::max(k, 1);
     mpo::WsCarver c(ws);
@@ -1436,6 +1740,7 @@ inline ScoreWs carve_score_ws(void* ws, int64_t m, int k, size_t* used) {
     w.tail_idx = c.take<long long>(3 * kk);
     w.tail_val = c.take<double>(3 * kk);
     w.mq = c.take<double>((size_t)m * 2);
+    w.part = c.take<double>(part_elems);
     if (used) *used = c.used;
     return w;
 }
@@ -1478,7 +1783,7 @@ int mpo_trsm_f64(const double* L, int n, int lda, double* B, int nrhs, int ldb, 
 
 size_t mpo_gp_prepare_ws_bytes(int n, int d) {
     const int dp = pad_dims(d);
-    if (n <= 0 || dp < 0) return 0;
+    if (n <= 0 || n > kScoreMaxN || dp < 0) return 0;
     const int np16 = (n + 15) / 16 * 16;
     const int xrows = np16 + 32;           // the scoring kernel reads one 16-row step past np16
     mpo::WsCarver c(nullptr);
@@ -1512,7 +1817,9 @@ int mpo_gp_prepare(const double* X, const double* y_norm, int n, int d, const do
                   ws_bytes, mpo_gp_prepare_ws_bytes(n, d));
     const int np16 = (n + 15) / 16 * 16;
     const int xrows = np16 + 32;
-    if (!score_fits(dp, np16)) { mpo::set_error("mpo_gp_prepare: n=%d exceeds the LDS-resident scoring limit", n); return MPO_ENOTSUP; }
+    if (n > kScoreMaxN) { mpo::set_error("mpo_gp_prepare: n=%d exceeds the supported maximum of %d observations", n, kScoreMaxN); return MPO_ENOTSUP; }
+    const int plan = score_plan(n, dp, np16, nullptr);
+    if (plan < 0) { mpo::set_error("mpo_gp_prepare: MPO_GP_PANEL must be a multiple of 16, >= 16"); return -plan; }
     hipStream_t s = static_cast<hipStream_t>(stream);
     mpo::WsCarver c(ws);
     double* xs = c.take<double>((size_t)xrows * dp);
@@ -1552,7 +1859,8 @@ int mpo_gp_prepare(const double* X, const double* y_norm, int n, int d, const do
     // themselves both ways, (mu_n, q) agree within 1e-10; candidate tiles with some
     // |c|^2 > kDistNorm take the direct form in the kernel.  MPO_GP_DIST=0: never.
     const char* de = getenv("MPO_GP_DIST");
-    const bool use_xb = d + 2 <= dp && !(de && de[0] == '0');
+    // A streamed model (score_plan) always scores with the direct form: no xb, no self-check.
+    const bool use_xb = plan == 0 && d + 2 <= dp && !(de && de[0] == '0');
     bool xb_set = false;
     if (use_xb) {
         double* flag = xb + (size_t)xrows * dp;
@@ -1602,9 +1910,11 @@ int mpo_gp_prepare(const double* X, const double* y_norm, int n, int d, const do
 
 size_t mpo_gp_score_ws_bytes(const MpoGpModel* model, int64_t m, int k) {
     if (!model || m <= 0 || k < 0 || k > MPO_TOPK_MAX) return 0;
-    if (!score_fits(model->dp, model->np16)) return 0;
+    int panel = 0;
+    const int plan = score_plan(model->n, model->dp, model->np16, &panel);
+    if (plan < 0) return 0;
     size_t used = 0;
-    carve_score_ws(nullptr, m, k, &used);
+    carve_score_ws(nullptr, m, k, &used, plan == 1 ? streamed_part_elems(model->dp, model->np16, panel, m) : 0);
     return used + 256;
 }
 
@@ -1619,11 +1929,19 @@ static int gp_score_impl(const MpoGpModel* model, const double* cand, int64_t m,
     MPO_CHECK_ARG(k == 0 || (topk_idx && topk_val), "mpo_gp_acq_score: topk outputs required for k>0");
     MPO_CHECK_ARG(k > 0 || mu || sd || vals, "mpo_gp_acq_score: nothing to compute");
     MPO_CHECK_ARG(ws && ws_bytes >= mpo_gp_score_ws_bytes(model, m, k), "mpo_gp_acq_score: workspace too small");
-    if (!score_fits(model->dp, model->np16)) { mpo::set_error("mpo_gp_acq_score: model too large"); return MPO_ENOTSUP; }
+    int panel = 0;
+    const int plan = score_plan(model->n, model->dp, model->np16, &panel);
+    if (plan < 0) {
+        mpo::set_error(plan == -MPO_ENOTSUP ? "mpo_gp_acq_score: n=%d exceeds the supported maximum of %d observations"
+                                            : "mpo_gp_acq_score: malformed model (n=%d) or MPO_GP_PANEL (a multiple of 16, >= 16; max n %d)",
+                       model->n, kScoreMaxN);
+        return -plan;
+    }
     const int64_t ntiles64 = (m + kBM - 1) / kBM;
     MPO_CHECK_ARG(ntiles64 < (1LL << 31), "mpo_gp_acq_score: too many candidates");
     const int ntiles = (int)ntiles64;
-    const ScoreWs w = carve_score_ws(ws, m, k, nullptr);
+    const ScoreWs w = carve_score_ws(ws, m, k, nullptr,
+                                     plan == 1 ? streamed_part_elems(model->dp, model->np16, panel, m) : 0);
     long long* part_idx = w.part_idx;
     double* part_val = w.part_val;
     long long* mid_idx = w.mid_idx;
@@ -1662,9 +1980,15 @@ static int gp_score_impl(const MpoGpModel* model, const double* cand, int64_t m,
     a.part_idx = part_idx;
     a.part_val = part_val;
     a.mq = w.mq;   // FIN: the workgroup's own rows, finished inside the scoring kernel
-    const size_t lds = score_lds_bytes(model->dp, model->np16);
+    a.panel = panel;
+    a.part = w.part;
     int grid = 0;
-    MPO_HIP(launch_score_dp(model->dp, model->d, a, ntiles, lds, s, /*fin=*/true, &grid));
+    if (plan == 1) {
+        MPO_HIP(launch_streamed_dp(model->dp, model->d, a, ntiles, s, &grid));
+    } else {
+        const size_t lds = score_lds_bytes(model->dp, model->np16);
+        MPO_HIP(launch_score_dp(model->dp, model->d, a, ntiles, lds, s, /*fin=*/true, &grid));
+    }
     const int nparts = 4 * grid;
     if (k > 0) {
         // stage 1: G groups of ~64 wave-lists each; stage 2: one list
@@ -1678,6 +2002,11 @@ static int gp_score_impl(const MpoGpModel* model, const double* cand, int64_t m,
         MPO_LAUNCH_CHECK();
     }
     return MPO_OK;
+}
+
+int mpo_gp_score_path(const MpoGpModel* model) {
+    if (!model) return -MPO_EINVAL;
+    return score_plan(model->n, model->dp, model->np16, nullptr);
 }
 
 int mpo_gp_acq_score(const MpoGpModel* model, const double* cand, int64_t m, double y_opt, double xi,
@@ -1694,9 +2023,14 @@ int mpo_gp_ei_score(const MpoGpModel* model, const double* cand, int64_t m, doub
                     void* stream) {
     MPO_GUARD_BEGIN
     MPO_CHECK_ARG(argmax, "mpo_gp_ei_score: null argmax");
+    MPO_CHECK_ARG(model && m > 0, "mpo_gp_ei_score: null model or m <= 0");
+    if (model->n > kScoreMaxN) {
+        mpo::set_error("mpo_gp_ei_score: n=%d exceeds the supported maximum of %d observations", model->n, kScoreMaxN);
+        return MPO_ENOTSUP;
+    }
+    MPO_CHECK_ARG(mpo_gp_score_ws_bytes(model, m, 1) != 0, "mpo_gp_ei_score: malformed model or MPO_GP_PANEL");
     MPO_CHECK_ARG(ws_bytes >= mpo_gp_score_ws_bytes(model, m, 1), "mpo_gp_ei_score: workspace too small");
     // top-1 of -EI lands in the tail of the workspace the score call does not use
-    if (!score_fits(model->dp, model->np16)) { mpo::set_error("mpo_gp_ei_score: model too large"); return MPO_ENOTSUP; }
     const ScoreWs w = carve_score_ws(ws, m, 1, nullptr);
     long long* tidx = w.tail_idx;
     double* tval = w.tail_val;

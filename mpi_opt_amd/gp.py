@@ -64,7 +64,7 @@ class DeviceGP:
         self._ls = torch.from_numpy(ls).to(self.device)
         wsb = L.mpo_gp_prepare_ws_bytes(n, d)
         if wsb == 0:
-            raise _lib.MpoError(f"unsupported GP shape n={n} d={d}")
+            raise _lib.MpoError(f"unsupported GP shape n={n} d={d} (n <= 2048, d <= 32)")
         self._ws = torch.empty(wsb, dtype=torch.uint8, device=self.device)
         self.model = _lib.MpoGpModel()
         with torch.cuda.device(self.device):
@@ -129,6 +129,13 @@ class DeviceGP:
         return self._state_view(self.model.alpha, self.n)
 
     # -- scoring ---------------------------------------------------------------
+    @property
+    def score_path(self):
+        """``mpo_gp_score_path``: 0 when ``score`` / ``ei_argmax`` run the LDS-resident
+        kernel for this model, 1 for the streamed one (models past the LDS limit, or
+        ``MPO_GP_SCORE=streamed``), negative when the model cannot be scored."""
+        return int(lib().mpo_gp_score_path(ctypes.byref(self.model)))
+
     def _ensure_ws(self, m, k):
         need = lib().mpo_gp_score_ws_bytes(ctypes.byref(self.model), int(m), int(k))
         if need == 0:

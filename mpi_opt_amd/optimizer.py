@@ -173,6 +173,19 @@ def _record_refit(n, t_refit, t_prepare, t_score, t_polish, t_propose, t_total):
 
 STRATEGIES = ("cl_min", "cl_mean", "cl_max")
 
+#: the most observations one GP takes (the refit's and the scoring kernels' bound in libmpo.so)
+MAX_GP_POINTS = 2048
+
+
+def _check_gp_size(n_told, n_lies=0):
+    """One clear error before any device work when a refit would see more than
+    MAX_GP_POINTS observations: told points plus the lies of the running batch."""
+    if n_told + n_lies > MAX_GP_POINTS:
+        raise ValueError(
+            f"the GP surrogate takes at most {MAX_GP_POINTS} observations, got n = {n_told + n_lies} "
+            f"({n_told} told points + {n_lies} constant-liar lies; the lies of the running "
+            "ask(n_points) batch count towards n)")
+
 
 class ChainJob:
     """Everything one ``ask(n_points, strategy)`` batch depends on: the optimizer's
@@ -382,6 +395,8 @@ class Optimizer:
             raise ValueError(f"strategy {strategy!r}")
         if (n_points, strategy) in self.cache_:
             return self.cache_[(n_points, strategy)]
+        if self.base_estimator_ == "gp" and self._n_initial_points - n_points <= 0:
+            _check_gp_size(len(self.yi), n_points)      # every lie is told to the copy, the last one too
         job = ChainJob(self, self.rng.randint(0, np.iinfo(np.int32).max), n_points, strategy)
         if self.chain_executor is not None:
             X = self.chain_executor.submit(job)
@@ -415,7 +430,11 @@ class Optimizer:
         return self._tell(x, y, fit=fit)
 
     def _tell(self, x, y, fit=True):
-        if len(x) and isinstance(x[0], (list, tuple, np.ndarray)):
+        batch = len(x) and isinstance(x[0], (list, tuple, np.ndarray))
+        n_new = len(y) if batch else 1
+        if fit and self._n_initial_points - n_new <= 0 and self.base_estimator_ == "gp":
+            _check_gp_size(len(self.yi) + n_new)        # before the points are taken: nothing changes on error
+        if batch:
             self.Xi.extend([list(v) for v in x])
             self.yi.extend([float(v) for v in y])
             self._n_initial_points -= len(y)
