@@ -201,9 +201,20 @@ __device__ __forceinline__ void wave_lex_min(double& v, long long& i) {
     }
 }
 
+// Sum over the 16 lanes of a row group: with the f64 MFMA C/D map (col = lane & 15,
+// row = (lane >> 4) + 4 r) the sum of a C register over the tile's 16 columns.
+__device__ __forceinline__ double colsum16(double v) {
+    v += __shfl_xor(v, 1);
+    v += __shfl_xor(v, 2);
+    v += __shfl_xor(v, 4);
+    v += __shfl_xor(v, 8);
+    return v;
+}
+
 // Rows [n, rows) of xs are zero padding (alpha and the L^-1 fragments are zero
 // there): a scoring loop may run over whole 16-observation groups without bounds
 // checks; the padding K* values are finite and contribute nothing.
+constexpr int kXsPadRows = 32;   // rows = np16 + kXsPadRows: the scoring kernel reads one 16-row step past np16
 
 __global__ void scale_rows_kernel(const double* __restrict__ X, int n, int rows, int d, int dp,
                                   const double* __restrict__ ls, double* __restrict__ xs,
@@ -508,6 +519,75 @@ __device__ __attribute__((noinline)) void score_finish_group(const ScoreArgs& a,
     }
 }
 
+// The finish of a looped scoring kernel (tiles blockIdx.x, += gridDim.x): this
+// workgroup's own (mu_n, q) rows (written in its tile loop, mostly still in this
+// XCD's L2), 64 candidates per wave at a time with every lane live; one running
+// top-k list per wave in the (now free) K* LDS region kc, written out as partial
+// lists 4 blockIdx.x + wave.
+// The finish reads its arguments through a pointer to the kernarg segment: the
+// out-of-line score_finish_group given `a` itself would copy the by-value struct to
+// the stack (and the scoring variants must stay scratch-free, see launch_looped);
+// the asm keeps the loads out of the tile loop.  This holds only for a kernel whose
+// only argument is one by-value ScoreArgs.
+__device__ __forceinline__ void score_finish_own_rows(double* kc, int wave, int lane) {
+    constexpr int BM = kBM;
+    __syncthreads();   // the rows of the tile loop (global writes, workgroup-scope visibility)
+    const ScoreArgs* ap = (const ScoreArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ap));
+    const ScoreArgs& f = *ap;
+    double* tk_val = kc + wave * 3 * MPO_TOPK_MAX;
+    long long* tk_idx = reinterpret_cast<long long*>(kc + 4 * 3 * MPO_TOPK_MAX) + wave * 3 * MPO_TOPK_MAX;
+    if (lane < 3 * MPO_TOPK_MAX) {
+        tk_val[lane] = __builtin_huge_val();
+        tk_idx[lane] = 0x7fffffffffffffffLL;
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    const long long ntl = ((f.m + BM - 1) / BM - blockIdx.x + gridDim.x - 1) / gridDim.x;   // this workgroup's tiles
+    for (long long c0 = (long long)wave * 64; c0 < ntl * BM; c0 += 256) {
+        const long long cl = c0 + lane;
+        const long long gm = (blockIdx.x + (cl >> 4) * (long long)gridDim.x) * BM + (cl & 15);
+        const bool valid = cl < ntl * BM && gm < f.m;
+        double2 v = {0.0, 0.0};
+        if (valid) v = *reinterpret_cast<const double2*>(f.mq + 2 * gm);
+        score_finish_group(f, valid, gm, v.x, v.y, lane, tk_val, tk_idx);
+    }
+    if (f.k > 0 && lane < 3 * f.k) {
+        const int acq = lane / f.k, r = lane - acq * f.k;
+        const size_t part = (size_t)blockIdx.x * 4 + wave;
+        f.part_val[(part * 3 + acq) * f.k + r] = tk_val[acq * MPO_TOPK_MAX + r];
+        f.part_idx[(part * 3 + acq) * f.k + r] = tk_idx[acq * MPO_TOPK_MAX + r];
+    }
+}
+
+// Pieces of both scoring kernels' bodies (macros: they read and update the
+// kernels' locals c, row, kc, mu_acc, acc0, acc1).
+// One group of B fragments (4 k-steps x 64 lanes of the wfrag stream) at lane
+// pointer P into the ring slot B[0..3]: asm loads the compiler cannot see or wait
+// for; every use of B is tied to an explicit s_waitcnt vmcnt (tests/test_isa_ring.py
+// checks the generated code of both kernels).
+#define MPO_LD(D, P, OFF) asm volatile("global_load_dwordx2 %0, %1, off offset:" #OFF : "=v"(D) : "v"(P) : "memory")
+#define MPO_LD4(B, P) { MPO_LD(B[0], P, 0); MPO_LD(B[1], P, 512); MPO_LD(B[2], P, 1024); MPO_LD(B[3], P, 1536); }
+// 4 MFMAs of one group on two accumulation chains: A fragments at lane pointer AP
+// (k-steps 64 doubles apart), B fragments B0..B3
+#define MPO_MFMA4(AP, B0, B1, B2, B3)                                                              \
+    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((AP)[0], B0, acc0, 0, 0, 0);                       \
+    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((AP)[64], B1, acc1, 0, 0, 0);                      \
+    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64((AP)[128], B2, acc0, 0, 0, 0);                     \
+    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64((AP)[192], B3, acc1, 0, 0, 0);
+// one observation row on the direct distance: r2, Matern, mu partial, K* into the
+// LDS at (panel-local) observation index LI
+#define MPO_EI_PAIR(XC, AC, LI)                                                                    \
+    {                                                                                              \
+        double r2 = kR2Floor;                                                                      \
+        _Pragma("unroll") for (int q = 0; q < D; ++q) {                                            \
+            const double t = c[q] - XC[q];                                                         \
+            r2 = fma(t, t, r2);                                                                    \
+        }                                                                                          \
+        const double kv = matern52_unit(r2);   /* amp folded into mu and q */                      \
+        mu_acc = fma(kv, AC, mu_acc);                                                              \
+        kc[(size_t)((LI) >> 2) * 64 + row + ((LI) & 3) * 16] = kv;                                 \
+    }
+
 // One workgroup = 4 waves looping over 16-candidate tiles (kBM) tile = blockIdx.x,
 // += gridDim.x (the grid is sized to the resident capacity); the next tile's
 // candidate rows are loaded while the current one is scored.
@@ -575,8 +655,6 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
     const int32_t* mw = mls + sw * (a.T + 4);        // LDS: no vmcnt wait at tile ends
     const int G = (a.dbg & 1) ? 0 : __builtin_amdgcn_readfirstlane(mw[1]);
     const double* bs = a.wfrag + (size_t)__builtin_amdgcn_readfirstlane(mw[0]) * 256 + lane;
-#define MPO_LD(D, P, OFF) asm volatile("global_load_dwordx2 %0, %1, off offset:" #OFF : "=v"(D) : "v"(P) : "memory")
-#define MPO_LD4(B, P) { MPO_LD(B[0], P, 0); MPO_LD(B[1], P, 512); MPO_LD(B[2], P, 1024); MPO_LD(B[3], P, 1536); }
 
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const long long m0 = tile * BM;
@@ -589,8 +667,9 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
     __syncthreads();
 
     // ---- phase 1: K*[row][i] (Matern52) in A-fragment order, mu partials.  xs and
-    // alpha hold far-away / zero rows up to np16 + 16: no bounds check on i, and the
-    // next observation row is loaded while the current one is evaluated.
+    // alpha are zero from row n to np16 + kXsPadRows (the note above
+    // scale_rows_kernel): no bounds check on i, and the next observation row is
+    // loaded while the current one is evaluated.
     {
         const int row = lane & 15;
         const int slot = wave * 4 + (lane >> 4);
@@ -637,14 +716,7 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
                     }
                 }
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    double v = mu4[r];
-                    v += __shfl_xor(v, 1);
-                    v += __shfl_xor(v, 2);
-                    v += __shfl_xor(v, 4);
-                    v += __shfl_xor(v, 8);
-                    mu4[r] = v;
-                }
+                for (int r = 0; r < 4; ++r) mu4[r] = colsum16(mu4[r]);
                 // this wave's 4 slots: the sum in slot 0, zeros in 1..3 (the mu fold below
                 // sums all 16 slots in order)
                 if ((lane & 15) == 0) {
@@ -659,23 +731,10 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
         } else if (a.dbg & 2) {
             for (int i = slot; i < np16; i += S) kc[(size_t)(i >> 2) * 64 + row + (i & 3) * 16] = c[0];
         } else {
-            // one observation row: r2, Matern, mu partial, K* into LDS
-#define MPO_EI_PAIR(XC, AC, I)                                                                     \
-            {                                                                                      \
-                double r2 = kR2Floor;                                                              \
-                _Pragma("unroll") for (int q = 0; q < D; ++q) {                                    \
-                    const double t = c[q] - XC[q];                                                 \
-                    r2 = fma(t, t, r2);                                                            \
-                }                                                                                  \
-                const double kv = matern52_unit(r2);   /* amp folded into mu and q below */        \
-                mu_acc = fma(kv, AC, mu_acc);                                                      \
-                kc[(size_t)((I) >> 2) * 64 + row + ((I) & 3) * 16] = kv;                           \
-            }
             for (int i = slot; i < np16; i += S) {
                 const double* xr = a.xs + (size_t)i * DP;
                 MPO_EI_PAIR(xr, a.alpha[i], i)
             }
-#undef MPO_EI_PAIR
         }
         if (!md || (a.dbg & 2)) red[slot * BM + row] = mu_acc;
     }
@@ -707,10 +766,7 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
         {                                                                                          \
             asm volatile("s_waitcnt vmcnt(4)" : "+v"(B[0]), "+v"(B[1]), "+v"(B[2]), "+v"(B[3])); \
             const double* ap = kl + kg * 256;                                                      \
-            acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[0], B[0], acc0, 0, 0, 0);              \
-            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[64], B[1], acc1, 0, 0, 0);             \
-            acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[128], B[2], acc0, 0, 0, 0);            \
-            acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(ap[192], B[3], acc1, 0, 0, 0);            \
+            MPO_MFMA4(ap, B[0], B[1], B[2], B[3])                                                  \
             MPO_LD4(B, bp);                                                                        \
             bp += 256;                                                                             \
             if (++kg == tlen) {                                                                    \
@@ -735,11 +791,7 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
         // f64 C/D map: col = lane & 15, row = (lane >> 4) + 4 r.  Sum the columns.
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            double v = sq[r];
-            v += __shfl_xor(v, 1);
-            v += __shfl_xor(v, 2);
-            v += __shfl_xor(v, 4);
-            v += __shfl_xor(v, 8);
+            const double v = colsum16(sq[r]);
             if ((lane & 15) == 0) red[wave * BM + (lane >> 4) + 4 * r] = v;
         }
     }
@@ -753,43 +805,7 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
         *reinterpret_cast<double2*>(a.mq + 2 * (m0 + lane)) = double2{mu_n, q};
     }
     }  // tile loop
-    if constexpr (FIN) {
-        // ---- finish: this workgroup's own (mu_n, q) rows (written above, mostly still
-        // in this XCD's L2), 64 candidates per wave at a time with every lane live;
-        // one running top-k list per wave in the (now free) K* LDS region
-        __syncthreads();   // the rows of wave fw (global writes, workgroup-scope visibility)
-        // the finish reads its arguments through a pointer to the kernarg segment: the
-        // out-of-line score_finish_group given `a` itself would copy the by-value
-        // struct to the stack (and the scoring variants must stay scratch-free, see
-        // launch_score); the asm keeps the loads out of the tile loop
-        const ScoreArgs* ap = (const ScoreArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-        asm volatile("" : "+s"(ap));
-        const ScoreArgs& f = *ap;
-        double* tk_val = kc + wave * 3 * MPO_TOPK_MAX;
-        long long* tk_idx = reinterpret_cast<long long*>(kc + 4 * 3 * MPO_TOPK_MAX) + wave * 3 * MPO_TOPK_MAX;
-        if (lane < 3 * MPO_TOPK_MAX) {
-            tk_val[lane] = __builtin_huge_val();
-            tk_idx[lane] = 0x7fffffffffffffffLL;
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        const long long ntl = ((f.m + BM - 1) / BM - blockIdx.x + gridDim.x - 1) / gridDim.x;   // this workgroup's tiles
-        for (long long c0 = (long long)wave * 64; c0 < ntl * BM; c0 += 256) {
-            const long long cl = c0 + lane;
-            const long long gm = (blockIdx.x + (cl >> 4) * (long long)gridDim.x) * BM + (cl & 15);
-            const bool valid = cl < ntl * BM && gm < f.m;
-            double2 v = {0.0, 0.0};
-            if (valid) v = *reinterpret_cast<const double2*>(f.mq + 2 * gm);
-            score_finish_group(f, valid, gm, v.x, v.y, lane, tk_val, tk_idx);
-        }
-        if (f.k > 0 && lane < 3 * f.k) {
-            const int acq = lane / f.k, r = lane - acq * f.k;
-            const size_t part = (size_t)blockIdx.x * 4 + wave;
-            f.part_val[(part * 3 + acq) * f.k + r] = tk_val[acq * MPO_TOPK_MAX + r];
-            f.part_idx[(part * 3 + acq) * f.k + r] = tk_idx[acq * MPO_TOPK_MAX + r];
-        }
-    }
-#undef MPO_LD4
-#undef MPO_LD
+    if constexpr (FIN) score_finish_own_rows(kc, wave, lane);
 #undef MPO_LOAD_TILE
 }
 
@@ -817,8 +833,7 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
 // score workspace: n = 2048, dp = 12, panel 1232 -> 51 tiles x 2 KiB x 256
 // workgroups = 25.5 MiB (26 MiB at dp = 32, panel 1216; streamed_grid_cap keeps any
 // forced panel under 48 MiB).
-// The finish is the resident kernel's: own (mu_n, q) rows, score_finish_group, one
-// top-k list per wave.
+// The finish is the resident kernel's (score_finish_own_rows).
 template <int DP, int D>
 __global__ __launch_bounds__(256) void gp_score_streamed_kernel(ScoreArgs a) {
     constexpr int BM = kBM;
@@ -860,16 +875,8 @@ __global__ __launch_bounds__(256) void gp_score_streamed_kernel(ScoreArgs a) {
             // ---- phase 1: K*[row][r0..r1) in A-fragment order (panel-local k-steps)
             for (int i = t0 * 16 + slot; i < t1 * 16; i += S) {
                 const double* xr = a.xs + (size_t)i * DP;
-                double r2 = kR2Floor;
-#pragma unroll
-                for (int q = 0; q < D; ++q) {
-                    const double t = c[q] - xr[q];
-                    r2 = fma(t, t, r2);
-                }
-                const double kv = matern52_unit(r2);   // amp folded into mu and q below
-                mu_acc = fma(kv, a.alpha[i], mu_acc);
                 const int li = i - t0 * 16;
-                kc[(size_t)(li >> 2) * 64 + row + (li & 3) * 16] = kv;
+                MPO_EI_PAIR(xr, a.alpha[i], li)
             }
             __syncthreads();
             // ---- phase 2: this panel's k-steps of every column tile at or below it
@@ -894,19 +901,13 @@ __global__ __launch_bounds__(256) void gp_score_streamed_kernel(ScoreArgs a) {
 #define MPO_ST_LD(B, G)                                                                        \
                 {                                                                              \
                     const double* p = bp + (size_t)min((G), ng - 1) * 256;                     \
-                    asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(B[0]) : "v"(p) : "memory");              \
-                    asm volatile("global_load_dwordx2 %0, %1, off offset:512" : "=v"(B[1]) : "v"(p) : "memory");   \
-                    asm volatile("global_load_dwordx2 %0, %1, off offset:1024" : "=v"(B[2]) : "v"(p) : "memory");  \
-                    asm volatile("global_load_dwordx2 %0, %1, off offset:1536" : "=v"(B[3]) : "v"(p) : "memory");  \
+                    MPO_LD4(B, p)                                                              \
                 }
 #define MPO_ST_GROUP(B, G)                                                                     \
                 {                                                                              \
                     asm volatile("s_waitcnt vmcnt(8)" : "+v"(B[0]), "+v"(B[1]), "+v"(B[2]), "+v"(B[3]));  \
                     const double* q = ap + (size_t)(G) * 256;                                  \
-                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[0], B[0], acc0, 0, 0, 0);    \
-                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[64], B[1], acc1, 0, 0, 0);   \
-                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[128], B[2], acc0, 0, 0, 0);  \
-                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[192], B[3], acc1, 0, 0, 0);  \
+                    MPO_MFMA4(q, B[0], B[1], B[2], B[3])                                       \
                     MPO_ST_LD(B, (G) + 3)                                                      \
                 }
                 // The ring loop runs whole rotations only, without a branch in its body
@@ -921,10 +922,7 @@ __global__ __launch_bounds__(256) void gp_score_streamed_kernel(ScoreArgs a) {
                 for (int g = 0; g < rem; ++g) {
                     const double* p = bp + (size_t)g * 256;
                     const double* q = ap + (size_t)g * 256;
-                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[0], p[0], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[64], p[64], acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[128], p[128], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(q[192], p[192], acc1, 0, 0, 0);
+                    MPO_MFMA4(q, p[0], p[64], p[128], p[192])
                 }
                 for (int g = rem; g < ng; g += 3) {
                     MPO_ST_GROUP(b0, g)
@@ -954,11 +952,7 @@ __global__ __launch_bounds__(256) void gp_score_streamed_kernel(ScoreArgs a) {
         red[slot * BM + row] = mu_acc;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            double v = sq[r];
-            v += __shfl_xor(v, 1);
-            v += __shfl_xor(v, 2);
-            v += __shfl_xor(v, 4);
-            v += __shfl_xor(v, 8);
+            const double v = colsum16(sq[r]);
             if ((lane & 15) == 0) red[(S + wave) * BM + (lane >> 4) + 4 * r] = v;
         }
         __syncthreads();
@@ -974,34 +968,12 @@ __global__ __launch_bounds__(256) void gp_score_streamed_kernel(ScoreArgs a) {
         // red and cs are next written behind the next tile's barriers
     }
 
-    // ---- finish: as gp_score_kernel<.., FIN = 1>
-    __syncthreads();
-    const ScoreArgs* ap = (const ScoreArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(ap));
-    const ScoreArgs& f = *ap;
-    double* tk_val = kc + wave * 3 * MPO_TOPK_MAX;
-    long long* tk_idx = reinterpret_cast<long long*>(kc + 4 * 3 * MPO_TOPK_MAX) + wave * 3 * MPO_TOPK_MAX;
-    if (lane < 3 * MPO_TOPK_MAX) {
-        tk_val[lane] = __builtin_huge_val();
-        tk_idx[lane] = 0x7fffffffffffffffLL;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    const long long ntl = ((f.m + BM - 1) / BM - blockIdx.x + gridDim.x - 1) / gridDim.x;   // this workgroup's tiles
-    for (long long c0 = (long long)wave * 64; c0 < ntl * BM; c0 += 256) {
-        const long long cl = c0 + lane;
-        const long long gm = (blockIdx.x + (cl >> 4) * (long long)gridDim.x) * BM + (cl & 15);
-        const bool valid = cl < ntl * BM && gm < f.m;
-        double2 v = {0.0, 0.0};
-        if (valid) v = *reinterpret_cast<const double2*>(f.mq + 2 * gm);
-        score_finish_group(f, valid, gm, v.x, v.y, lane, tk_val, tk_idx);
-    }
-    if (f.k > 0 && lane < 3 * f.k) {
-        const int acq = lane / f.k, r = lane - acq * f.k;
-        const size_t part_i = (size_t)blockIdx.x * 4 + wave;
-        f.part_val[(part_i * 3 + acq) * f.k + r] = tk_val[acq * MPO_TOPK_MAX + r];
-        f.part_idx[(part_i * 3 + acq) * f.k + r] = tk_idx[acq * MPO_TOPK_MAX + r];
-    }
+    score_finish_own_rows(kc, wave, lane);
 }
+#undef MPO_EI_PAIR
+#undef MPO_MFMA4
+#undef MPO_LD4
+#undef MPO_LD
 
 // Merge per-block top-k lists.  grid = (G, 3): block g of acquisition y merges
 // the partial lists [g*chunk, min((g+1)*chunk, nparts)) and writes one list.
@@ -1083,12 +1055,18 @@ __global__ void argmax_from_topk_kernel(const long long* __restrict__ topk_idx, 
     *argmax = topk_idx[0];
 }
 
+// The (padded row width DP, distance dims D) instances of the scoring kernels, DP
+// ascending: d = 5 and d = 10 (the reference's mnist space and the BASELINE config)
+// get exact-width distance loops, listed ahead of their width's general instance.
+// pad_dims, score_plan's test of a model's width and launch_scoring's dispatch all
+// read this list.
+#define MPO_SCORE_DIMS(X) X(4, 4) X(8, 5) X(8, 8) X(12, 10) X(12, 12) X(16, 16) X(32, 32)
+
+// padded row width of d dims; -1 past the widest
 inline int pad_dims(int d) {
-    if (d <= 4) return 4;
-    if (d <= 8) return 8;
-    if (d <= 12) return 12;
-    if (d <= 16) return 16;
-    if (d <= 32) return 32;
+#define MPO_X(DP, D) if (d <= DP) return DP;
+    MPO_SCORE_DIMS(MPO_X)
+#undef MPO_X
     return -1;
 }
 
@@ -1107,38 +1085,12 @@ size_t score_lds_bytes(int dp, int np16) {
 
 bool score_fits(int dp, int np16) { return score_lds_bytes(dp, np16) <= kMaxLds; }
 
-// ---- streamed path (gp_score_streamed_kernel): models past score_fits, n <= kScoreMaxN
-constexpr int kScoreMaxN = 2048;                  // = kFitMaxN of the refit (gp_fit.hip)
+// ---- streamed path (gp_score_streamed_kernel): models past score_fits, n <= mpo::kMaxObs
 constexpr size_t kStreamPartCap = (size_t)48 << 20;   // bytes of partial rows per scoring call
 
 // one K* panel, cs, red (mu slots + q) | tile offsets
 size_t streamed_lds_bytes(int dp, int np16, int panel) {
     return ((size_t)panel * kBM + (size_t)kBM * dp + 20 * kBM) * sizeof(double) + (size_t)(np16 / 16) * sizeof(int32_t);
-}
-
-// Which scoring kernel serves a model: 0 resident, 1 streamed (*panel = its panel
-// rows), -MPO_ENOTSUP past kScoreMaxN, -MPO_EINVAL for a malformed model or switch.
-// Host arithmetic only.  MPO_GP_SCORE=streamed forces the streamed kernel at any n
-// ("resident" or unset: resident whenever it fits); MPO_GP_PANEL=<rows> (a multiple
-// of 16, >= 16) sets the panel, clamped to the largest one that fits the LDS.
-int score_plan(int n, int dp, int np16, int* panel) {
-    if (n <= 0 || np16 < n || np16 - n >= 16 || (np16 & 15) ||
-        !(dp == 4 || dp == 8 || dp == 12 || dp == 16 || dp == 32))
-        return -MPO_EINVAL;
-    if (n > kScoreMaxN) return -MPO_ENOTSUP;
-    const char* e = getenv("MPO_GP_SCORE");
-    const bool forced = e && std::string(e) == "streamed";
-    if (!forced && score_fits(dp, np16)) return 0;
-    int p = np16;
-    while (p > 16 && streamed_lds_bytes(dp, np16, p) > kMaxLds) p -= 16;
-    if (const char* pe = getenv("MPO_GP_PANEL"); pe && *pe) {
-        char* end = nullptr;
-        const long v = strtol(pe, &end, 10);
-        if (*end || v < 16 || v % 16) return -MPO_EINVAL;
-        p = (int)std::min<long>(p, v);
-    }
-    if (panel) *panel = p;
-    return 1;
 }
 
 // Streamed grid bound, from host arithmetic only (the workspace query runs without a
@@ -1152,24 +1104,73 @@ int streamed_grid_cap(int dp, int np16, int panel) {
     return cap;
 }
 
-// grid = the device's resident capacity for this variant (tiles are looped over);
-// *grid_out receives it (FIN: one top-k list per workgroup)
-template <int DP, int D, int OCC, int MD, int FIN>
-hipError_t launch_score(const ScoreArgs& a, int ntiles, size_t lds, hipStream_t s, int* grid_out) {
-    auto kern = gp_score_kernel<DP, D, OCC, MD, FIN>;
-    // The B ring's asm loads are invisible to the compiler: a spill of a ring
-    // register would store it before its load lands.  A variant whose register
-    // cap forces spills is refused instead of run.
+// What serves one scoring call: built once per entry point by score_plan.
+struct ScorePlan {
+    int path;            // 0 resident (gp_score_kernel), 1 streamed (gp_score_streamed_kernel)
+    int panel;           // streamed: observation rows per K* panel
+    size_t lds;          // the kernel's dynamic LDS bytes
+    int grid_cap;        // grid bound the workspace is sized from (the launch may stay below it)
+    size_t part_elems;   // streamed: doubles of partial rows for the call's m candidates
+};
+
+// The plan for scoring m candidates against a model, or the refusal: MPO_ENOTSUP
+// past mpo::kMaxObs, MPO_EINVAL for a malformed model or switch, with the message
+// set under the entry point's name `who` (null: a silent query).  Host arithmetic
+// only.  MPO_GP_SCORE=streamed forces the streamed kernel at any n ("resident" or
+// unset: resident whenever it fits); MPO_GP_PANEL=<rows> (a multiple of 16, >= 16)
+// sets the panel, clamped to the largest one that fits the LDS.
+int score_plan(const char* who, const MpoGpModel* model, int64_t m, ScorePlan* plan) {
+    const int n = model->n, dp = model->dp, np16 = model->np16;
+    auto refuse = [&](int rc) {
+        if (who)
+            mpo::set_error(rc == MPO_ENOTSUP
+                               ? "%s: n=%d exceeds the supported maximum of %d observations"
+                               : "%s: malformed model (n=%d) or MPO_GP_PANEL (a multiple of 16, >= 16; max n %d)",
+                           who, n, mpo::kMaxObs);
+        return rc;
+    };
+    if (n <= 0 || np16 < n || np16 - n >= 16 || (np16 & 15) || dp <= 0 || pad_dims(dp) != dp)
+        return refuse(MPO_EINVAL);   // pad_dims is the identity on the supported widths only
+    if (n > mpo::kMaxObs) return refuse(MPO_ENOTSUP);
+    const char* e = getenv("MPO_GP_SCORE");
+    const bool forced = e && std::string(e) == "streamed";
+    if (!forced && score_fits(dp, np16)) {
+        *plan = ScorePlan{0, 0, score_lds_bytes(dp, np16), kScoreGridCap, 0};
+        return MPO_OK;
+    }
+    int p = np16;
+    while (p > 16 && streamed_lds_bytes(dp, np16, p) > kMaxLds) p -= 16;
+    if (const char* pe = getenv("MPO_GP_PANEL"); pe && *pe) {
+        char* end = nullptr;
+        const long v = strtol(pe, &end, 10);
+        if (*end || v < 16 || v % 16) return refuse(MPO_EINVAL);
+        p = (int)std::min<long>(p, v);
+    }
+    const int cap = streamed_grid_cap(dp, np16, p);
+    const int64_t grid = std::min<int64_t>((m + kBM - 1) / kBM, cap);
+    *plan = ScorePlan{1, p, streamed_lds_bytes(dp, np16, p), cap, (size_t)grid * (size_t)(np16 - p) * kBM};
+    return MPO_OK;
+}
+
+using ScoreKernel = void (*)(ScoreArgs);
+
+// One launch of a looped scoring kernel (tiles blockIdx.x, += gridDim.x): grid =
+// min(tiles, cap (the workspace is sized from it), the device's resident capacity
+// at this LDS size); *grid_out receives it (one top-k list per wave of the grid).
+// The B ring's asm loads are invisible to the compiler: a spill of a ring register
+// would store it before its load lands.  A variant that spills is refused instead
+// of run.
+hipError_t launch_looped(ScoreKernel kern, const ScoreArgs& a, int ntiles, size_t lds, int cap, hipStream_t s,
+                         int* grid_out) {
+    const void* fn = reinterpret_cast<const void*>(kern);
     hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern)) != hipSuccess || fa.localSizeBytes != 0)
-        return hipErrorInvalidDeviceFunction;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)lds);
+    if (hipFuncGetAttributes(&fa, fn) != hipSuccess || fa.localSizeBytes != 0) return hipErrorInvalidDeviceFunction;
+    (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     int dev = 0, cus = 0, per_cu = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 256, lds);
-    int grid = std::max(1, std::min(std::min(ntiles, kScoreGridCap), std::max(1, per_cu) * std::max(1, cus)));
+    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, lds);
+    const int grid = std::max(1, std::min(std::min(ntiles, cap), std::max(1, per_cu) * std::max(1, cus)));
     if (grid_out) *grid_out = grid;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
     return hipGetLastError();
@@ -1190,7 +1191,7 @@ bool spill_free() {
 // occupancy hint (min waves per SIMD -> VGPR cap): the highest spill-free one;
 // MPO_GP_OCC (2, 4, 5, 6) forces one for experiments
 template <int DP, int D, int MD, int FIN>
-hipError_t launch_score_occ_md(const ScoreArgs& a, int nblocks, size_t lds, hipStream_t s, int* grid_out) {
+ScoreKernel resident_kernel_occ() {
     const char* e = getenv("MPO_GP_OCC");
     int occ = e ? atoi(e) : 0;
     if (occ != 2 && occ != 4 && occ != 5 && occ != 6)
@@ -1199,10 +1200,10 @@ hipError_t launch_score_occ_md(const ScoreArgs& a, int nblocks, size_t lds, hipS
               : spill_free<DP, D, 4, MD, FIN>() ? 4
                                                 : 2;
     switch (occ) {
-        case 6: return launch_score<DP, D, 6, MD, FIN>(a, nblocks, lds, s, grid_out);
-        case 5: return launch_score<DP, D, 5, MD, FIN>(a, nblocks, lds, s, grid_out);
-        case 4: return launch_score<DP, D, 4, MD, FIN>(a, nblocks, lds, s, grid_out);
-        default: return launch_score<DP, D, 2, MD, FIN>(a, nblocks, lds, s, grid_out);
+        case 6: return gp_score_kernel<DP, D, 6, MD, FIN>;
+        case 5: return gp_score_kernel<DP, D, 5, MD, FIN>;
+        case 4: return gp_score_kernel<DP, D, 4, MD, FIN>;
+        default: return gp_score_kernel<DP, D, 2, MD, FIN>;
     }
 }
 
@@ -1210,69 +1211,28 @@ hipError_t launch_score_occ_md(const ScoreArgs& a, int nblocks, size_t lds, hipS
 // reads the self-check's device flag); MPO_GP_DIST=0 forces the direct form.
 // fin = false: raw (mu_n, q) rows only.
 template <int DP, int D>
-hipError_t launch_score_occ(const ScoreArgs& a, int nblocks, size_t lds, hipStream_t s, bool fin, int* grid_out) {
+ScoreKernel resident_kernel(const ScoreArgs& a, bool fin) {
     if constexpr (D + 2 <= DP) {
         const char* e = getenv("MPO_GP_DIST");
         if (a.xb && a.xb_ok && !(e && e[0] == '0'))
-            return fin ? launch_score_occ_md<DP, D, 1, 1>(a, nblocks, lds, s, grid_out)
-                       : launch_score_occ_md<DP, D, 1, 0>(a, nblocks, lds, s, grid_out);
+            return fin ? resident_kernel_occ<DP, D, 1, 1>() : resident_kernel_occ<DP, D, 1, 0>();
     }
-    return fin ? launch_score_occ_md<DP, D, 0, 1>(a, nblocks, lds, s, grid_out)
-               : launch_score_occ_md<DP, D, 0, 0>(a, nblocks, lds, s, grid_out);
+    return fin ? resident_kernel_occ<DP, D, 0, 1>() : resident_kernel_occ<DP, D, 0, 0>();
 }
 
-// (padded row width DP, distance dims D): d = 5 and d = 10 (the reference's mnist
-// space and the BASELINE config) get exact-width distance loops
-hipError_t launch_score_dp(int dp, int d, const ScoreArgs& a, int nblocks, size_t lds, hipStream_t s, bool fin,
-                           int* grid_out = nullptr) {
-    switch (dp) {
-        case 4: return launch_score_occ<4, 4>(a, nblocks, lds, s, fin, grid_out);
-        case 8: return d == 5 ? launch_score_occ<8, 5>(a, nblocks, lds, s, fin, grid_out)
-                              : launch_score_occ<8, 8>(a, nblocks, lds, s, fin, grid_out);
-        case 12: return d == 10 ? launch_score_occ<12, 10>(a, nblocks, lds, s, fin, grid_out)
-                                : launch_score_occ<12, 12>(a, nblocks, lds, s, fin, grid_out);
-        case 16: return launch_score_occ<16, 16>(a, nblocks, lds, s, fin, grid_out);
-        case 32: return launch_score_occ<32, 32>(a, nblocks, lds, s, fin, grid_out);
-    }
-    return hipErrorInvalidValue;
+// The plan's kernel for a model of padded width dp and d dims, launched over ntiles
+// candidate tiles (fin = false: the resident kernel only)
+hipError_t launch_scoring(int dp, int d, const ScorePlan& p, const ScoreArgs& a, int ntiles, hipStream_t s, bool fin,
+                          int* grid_out = nullptr) {
+    ScoreKernel kern = nullptr;
+#define MPO_X(DP, D)                                       \
+    if (!kern && dp == DP && (d == D || D == DP))          \
+        kern = p.path == 1 ? gp_score_streamed_kernel<DP, D> : resident_kernel<DP, D>(a, fin);
+    MPO_SCORE_DIMS(MPO_X)
+#undef MPO_X
+    if (!kern) return hipErrorInvalidValue;
+    return launch_looped(kern, a, ntiles, p.lds, p.grid_cap, s, grid_out);
 }
-
-// streamed kernel: grid = min(tiles, streamed_grid_cap (the workspace is sized from
-// it), the device's resident capacity).  The B ring's asm loads are invisible to the
-// compiler: a variant that spills is refused, as in launch_score.
-template <int DP, int D>
-hipError_t launch_streamed(const ScoreArgs& a, int ntiles, hipStream_t s, int* grid_out) {
-    auto kern = gp_score_streamed_kernel<DP, D>;
-    hipFuncAttributes fa;
-    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kern)) != hipSuccess || fa.localSizeBytes != 0)
-        return hipErrorInvalidDeviceFunction;
-    const size_t lds = streamed_lds_bytes(DP, a.np16, a.panel);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds);
-    int dev = 0, cus = 0, per_cu = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(kern), 256, lds);
-    const int grid = std::max(1, std::min(std::min(ntiles, streamed_grid_cap(DP, a.np16, a.panel)),
-                                          std::max(1, per_cu) * std::max(1, cus)));
-    if (grid_out) *grid_out = grid;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_streamed_dp(int dp, int d, const ScoreArgs& a, int ntiles, hipStream_t s, int* grid_out) {
-    switch (dp) {
-        case 4: return launch_streamed<4, 4>(a, ntiles, s, grid_out);
-        case 8: return d == 5 ? launch_streamed<8, 5>(a, ntiles, s, grid_out)
-                              : launch_streamed<8, 8>(a, ntiles, s, grid_out);
-        case 12: return d == 10 ? launch_streamed<12, 10>(a, ntiles, s, grid_out)
-                                : launch_streamed<12, 12>(a, ntiles, s, grid_out);
-        case 16: return launch_streamed<16, 16>(a, ntiles, s, grid_out);
-        case 32: return launch_streamed<32, 32>(a, ntiles, s, grid_out);
-    }
-    return hipErrorInvalidValue;
-}
-
 
 int trsm_cols_per_block(int n) {
     size_t cb = 64;
@@ -1716,19 +1676,15 @@ struct ScoreWs {
     double* tail_val;
     double* mq;
     double* part;   // streamed path: the workgroups' partial-row slices (part_elems doubles)
+    size_t used;    // bytes carved
 };
 
 // top-k lists: 4 per workgroup (one per wave); a workgroup has at least one tile
 // and the grid never exceeds kScoreGridCap (tiles are looped over)
 inline int64_t score_nparts(int64_t m) { return 4 * std::min<int64_t>((m + kBM - 1) / kBM, kScoreGridCap); }
 
-// doubles of partial rows a streamed scoring call over m candidates needs
-inline size_t streamed_part_elems(int dp, int np16, int panel, int64_t m) {
-    const int64_t grid = std::min<int64_t>((m + kBM - 1) / kBM, streamed_grid_cap(dp, np16, panel));
-    return (size_t)grid * (size_t)(np16 - panel) * kBM;
-}
-
-inline ScoreWs carve_score_ws(void* ws, int64_t m, int k, size_t* used, size_t part_elems = 0) {
+// ws = null: the size query (pointers null, used valid)
+inline ScoreWs carve_score_ws(void* ws, int64_t m, int k, size_t part_elems = 0) {
     const int64_t nparts = score_nparts(m);
     const int kk = std::max(k, 1);
     mpo::WsCarver c(ws);
@@ -1741,8 +1697,77 @@ inline ScoreWs carve_score_ws(void* ws, int64_t m, int k, size_t* used, size_t p
     w.tail_val = c.take<double>(3 * kk);
     w.mq = c.take<double>((size_t)m * 2);
     w.part = c.take<double>(part_elems);
-    if (used) *used = c.used;
+    w.used = c.used;
     return w;
+}
+
+// The prepare workspace: the model's arrays (MpoGpModel points into them, and
+// export_factor / from_factor ship these bytes between ranks: the order and sizes
+// are a format), the self-check's rows and the blocked factorisation's scratch.
+struct PrepareWs {
+    double* xs;        // [np16 + kXsPadRows][dp] (zero padding rows)
+    double* ls_pad;    // [dp]
+    double* L;         // [n][n]
+    double* W;         // [n][n]
+    double* alpha;     // [np16 + kXsPadRows] (zero padding)
+    double* wfrag;
+    int32_t* info;
+    int32_t* wmeta;
+    double* xb;        // [np16 + kXsPadRows][dp] + its guard flag (xb_flag)
+    double* mqc;       // [2][n][2] xb self-check (mu_n, q) rows, direct and expanded
+    double* Ab;        // blocked factorisation: padded A -> L
+    double* Wb;        //                        padded W
+    double* Db;        //                        diagonal-block inverses
+    double* vb;        //                        W y
+    size_t used;       // bytes carved
+};
+
+// ws = null: the size query (pointers null, used valid)
+inline PrepareWs carve_prepare_ws(void* ws, int n, int dp) {
+    const int np16 = (n + 15) / 16 * 16;
+    const size_t xrows = np16 + kXsPadRows, np = bc_np(n);
+    mpo::WsCarver c(ws);
+    PrepareWs w;
+    w.xs = c.take<double>(xrows * dp);
+    w.ls_pad = c.take<double>(dp);
+    w.L = c.take<double>((size_t)n * n);
+    w.W = c.take<double>((size_t)n * n);
+    w.alpha = c.take<double>(xrows);
+    w.wfrag = c.take<double>(wfrag_elems(np16));
+    w.info = c.take<int32_t>(4);
+    w.wmeta = c.take<int32_t>(wmeta_elems(np16));
+    w.xb = c.take<double>(xrows * dp + 8);
+    w.mqc = c.take<double>(4 * (size_t)n);
+    w.Ab = c.take<double>(np * np);
+    w.Wb = c.take<double>(np * np);
+    w.Db = c.take<double>(np * kBc);
+    w.vb = c.take<double>(np);
+    w.used = c.used;
+    return w;
+}
+
+// the expanded distance's device flag, behind the rows of xb (xb_kernel writes it)
+template <class T>
+inline T* xb_flag(T* xb, int np16, int dp) { return xb + (size_t)(np16 + kXsPadRows) * dp; }
+
+// The model's part of a scoring call's arguments; the call's own part is zero.
+inline ScoreArgs model_score_args(const MpoGpModel& md) {
+    ScoreArgs a{};
+    a.n = md.n;
+    a.np16 = md.np16;
+    a.T = md.np16 / 16;
+    a.d = md.d;
+    a.amp = md.amp;
+    a.y_mean = md.y_mean;
+    a.y_std = md.y_std;
+    a.xs = md.xs;
+    a.xb = md.xb;
+    a.xb_ok = md.xb ? xb_flag(md.xb, md.np16, md.dp) : nullptr;
+    a.ls = md.ls;
+    a.alpha = md.alpha;
+    a.wfrag = md.wfrag;
+    a.wmeta = md.wmeta;
+    return a;
 }
 
 }  // namespace
@@ -1783,26 +1808,8 @@ int mpo_trsm_f64(const double* L, int n, int lda, double* B, int nrhs, int ldb, 
 
 size_t mpo_gp_prepare_ws_bytes(int n, int d) {
     const int dp = pad_dims(d);
-    if (n <= 0 || n > kScoreMaxN || dp < 0) return 0;
-    const int np16 = (n + 15) / 16 * 16;
-    const int xrows = np16 + 32;           // the scoring kernel reads one 16-row step past np16
-    mpo::WsCarver c(nullptr);
-    c.take<double>((size_t)xrows * dp);    // xs (+ far-away padding rows)
-    c.take<double>(dp);                    // ls_pad
-    c.take<double>((size_t)n * n);         // L
-    c.take<double>((size_t)n * n);         // W
-    c.take<double>(xrows);                 // alpha (+ zero padding)
-    c.take<double>(wfrag_elems(np16));     // wfrag
-    c.take<int32_t>(4);                    // info
-    c.take<int32_t>(wmeta_elems(np16));    // wmeta
-    c.take<double>((size_t)xrows * dp + 8);   // xb + its guard flag
-    c.take<double>(4 * (size_t)n);            // xb self-check (mu_n, q) rows, direct and expanded
-    const size_t np = bc_np(n);
-    c.take<double>(np * np);                  // blocked factorisation: padded A -> L
-    c.take<double>(np * np);                  //                        padded W
-    c.take<double>(np * kBc);                 //                        diagonal-block inverses
-    c.take<double>(np);                       //                        W y
-    return c.used + 256;
+    if (n <= 0 || n > mpo::kMaxObs || dp < 0) return 0;
+    return carve_prepare_ws(nullptr, n, dp).used + 256;
 }
 
 int mpo_gp_prepare(const double* X, const double* y_norm, int n, int d, const double* ls,
@@ -1816,42 +1823,44 @@ int mpo_gp_prepare(const double* X, const double* y_norm, int n, int d, const do
     MPO_CHECK_ARG(ws_bytes >= mpo_gp_prepare_ws_bytes(n, d), "mpo_gp_prepare: workspace too small (%zu < %zu)",
                   ws_bytes, mpo_gp_prepare_ws_bytes(n, d));
     const int np16 = (n + 15) / 16 * 16;
-    const int xrows = np16 + 32;
-    if (n > kScoreMaxN) { mpo::set_error("mpo_gp_prepare: n=%d exceeds the supported maximum of %d observations", n, kScoreMaxN); return MPO_ENOTSUP; }
-    const int plan = score_plan(n, dp, np16, nullptr);
-    if (plan < 0) { mpo::set_error("mpo_gp_prepare: MPO_GP_PANEL must be a multiple of 16, >= 16"); return -plan; }
+    const int xrows = np16 + kXsPadRows;
+    MpoGpModel md{};
+    md.n = n;
+    md.d = d;
+    md.dp = dp;
+    md.np16 = np16;
+    md.amp = amp;
+    md.y_mean = y_mean;
+    md.y_std = y_std;
+    ScorePlan plan;
+    if (const int rc = score_plan("mpo_gp_prepare", &md, n, &plan)) return rc;
+    const PrepareWs w = carve_prepare_ws(ws, n, dp);
+    md.xs = w.xs;
+    md.ls = w.ls_pad;
+    md.alpha = w.alpha;
+    md.wfrag = w.wfrag;
+    md.L = w.L;
+    md.W = w.W;
+    md.info = w.info;
+    md.wmeta = w.wmeta;
+    md.xb = nullptr;   // set below once the self-check has run
     hipStream_t s = static_cast<hipStream_t>(stream);
-    mpo::WsCarver c(ws);
-    double* xs = c.take<double>((size_t)xrows * dp);
-    double* ls_pad = c.take<double>(dp);
-    double* L = c.take<double>((size_t)n * n);
-    double* W = c.take<double>((size_t)n * n);
-    double* alpha = c.take<double>(xrows);
-    double* wfrag = c.take<double>(wfrag_elems(np16));
-    int32_t* info = c.take<int32_t>(4);
-    int32_t* wmeta = c.take<int32_t>(wmeta_elems(np16));
-    double* xb = c.take<double>((size_t)xrows * dp + 8);
-    double* mqc = c.take<double>(4 * (size_t)n);
-    const size_t npb = bc_np(n);
-    double* Ab = c.take<double>(npb * npb);
-    double* Wb = c.take<double>(npb * npb);
-    double* Db = c.take<double>(npb * kBc);
-    double* vb = c.take<double>(npb);
 
-    hipLaunchKernelGGL(scale_rows_kernel, dim3((xrows * dp + 255) / 256), dim3(256), 0, s, X, n, xrows, d, dp, ls, xs,
-                       ls_pad);
+    hipLaunchKernelGGL(scale_rows_kernel, dim3((xrows * dp + 255) / 256), dim3(256), 0, s, X, n, xrows, d, dp, ls, w.xs,
+                       w.ls_pad);
     MPO_LAUNCH_CHECK();
-    hipLaunchKernelGGL(zero_kernel, dim3((xrows + 255) / 256), dim3(256), 0, s, alpha, xrows);
+    hipLaunchKernelGGL(zero_kernel, dim3((xrows + 255) / 256), dim3(256), 0, s, w.alpha, xrows);
     MPO_LAUNCH_CHECK();
-    MPO_HIP(blocked_factor(xs, n, dp, amp, noise + kJitter, y_norm, Ab, Wb, Db, vb, L, W, alpha, info, s));
+    MPO_HIP(blocked_factor(w.xs, n, dp, amp, noise + kJitter, y_norm, w.Ab, w.Wb, w.Db, w.vb, w.L, w.W, w.alpha, w.info,
+                           s));
     const int T = np16 / 16;
     const size_t nw = wfrag_elems(np16);
-    hipLaunchKernelGGL(zero_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, wfrag, (int)nw);
+    hipLaunchKernelGGL(zero_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w.wfrag, (int)nw);
     MPO_LAUNCH_CHECK();
-    hipLaunchKernelGGL(wave_plan_kernel, dim3(1), dim3(64), 0, s, T, wmeta);
+    hipLaunchKernelGGL(wave_plan_kernel, dim3(1), dim3(64), 0, s, T, w.wmeta);
     MPO_LAUNCH_CHECK();
-    hipLaunchKernelGGL(pack_wfrag_kernel, dim3((4 * T * 64 + 255) / 256, T), dim3(256), 0, s, W, n, n, T, wmeta,
-                       wfrag);
+    hipLaunchKernelGGL(pack_wfrag_kernel, dim3((4 * T * 64 + 255) / 256, T), dim3(256), 0, s, w.W, n, n, T, w.wmeta,
+                       w.wfrag);
     MPO_LAUNCH_CHECK();
     // The expanded (MFMA) distance |c|^2 + |x|^2 - 2 c.x (d + 2 <= dp) carries an absolute
     // error of a few eps (|c|^2 + |x|^2) instead of the direct form's eps r2.  Its device
@@ -1860,115 +1869,75 @@ int mpo_gp_prepare(const double* X, const double* y_norm, int n, int d, const do
     // |c|^2 > kDistNorm take the direct form in the kernel.  MPO_GP_DIST=0: never.
     const char* de = getenv("MPO_GP_DIST");
     // A streamed model (score_plan) always scores with the direct form: no xb, no self-check.
-    const bool use_xb = plan == 0 && d + 2 <= dp && !(de && de[0] == '0');
-    bool xb_set = false;
-    if (use_xb) {
-        double* flag = xb + (size_t)xrows * dp;
-        hipLaunchKernelGGL(xb_kernel, dim3(1), dim3(256), 0, s, xs, xrows, d, dp, xb);
+    if (plan.path == 0 && d + 2 <= dp && !(de && de[0] == '0')) {
+        double* flag = xb_flag(w.xb, np16, dp);
+        hipLaunchKernelGGL(xb_kernel, dim3(1), dim3(256), 0, s, w.xs, xrows, d, dp, w.xb);
         MPO_LAUNCH_CHECK();
-        ScoreArgs sa{};
-        sa.n = n; sa.np16 = np16; sa.T = T; sa.d = d;
-        sa.amp = amp; sa.y_mean = y_mean; sa.y_std = y_std;
-        sa.xs = xs; sa.ls = ls_pad; sa.alpha = alpha; sa.wfrag = wfrag; sa.wmeta = wmeta;
-        sa.cand = X; sa.m = n; sa.flags = 1;
+        ScoreArgs sa = model_score_args(md);           // md.xb still null: the direct form
+        sa.cand = X;
+        sa.m = n;
+        sa.flags = 1;
         const int nt = (n + kBM - 1) / kBM;
-        const size_t lds = score_lds_bytes(dp, np16);
-        sa.mq = mqc;                                   // direct form
-        bool ok = launch_score_dp(dp, d, sa, nt, lds, s, false) == hipSuccess;
-        sa.mq = mqc + 2 * (size_t)n;                   // expanded form
-        sa.xb = xb;
+        double* mqm = w.mqc + 2 * (size_t)n;
+        sa.mq = w.mqc;
+        bool ok = launch_scoring(dp, d, plan, sa, nt, s, /*fin=*/false) == hipSuccess;
+        sa.mq = mqm;                                   // expanded form
+        sa.xb = w.xb;
         sa.xb_ok = flag;
         // a refused variant (MPO_GP_OCC forcing a spilling one) just leaves xb out
-        ok = ok && launch_score_dp(dp, d, sa, nt, lds, s, false) == hipSuccess;
+        ok = ok && launch_scoring(dp, d, plan, sa, nt, s, /*fin=*/false) == hipSuccess;
         if (ok) {
-            hipLaunchKernelGGL(xb_check_kernel, dim3(1), dim3(256), 0, s, mqc, mqc + 2 * (size_t)n, alpha, n, amp,
-                               flag);
+            hipLaunchKernelGGL(xb_check_kernel, dim3(1), dim3(256), 0, s, w.mqc, mqm, w.alpha, n, amp, flag);
             MPO_LAUNCH_CHECK();
+            md.xb = w.xb;
         }
-        xb_set = ok;
     }
-
-    model->n = n;
-    model->d = d;
-    model->dp = dp;
-    model->np16 = np16;
-    model->amp = amp;
-    model->y_mean = y_mean;
-    model->y_std = y_std;
-    model->xs = xs;
-    model->ls = ls_pad;
-    model->alpha = alpha;
-    model->wfrag = wfrag;
-    model->L = L;
-    model->W = W;
-    model->info = info;
-    model->wmeta = wmeta;
-    model->xb = xb_set ? xb : nullptr;
+    *model = md;
     return MPO_OK;
     MPO_GUARD_END
 }
 
 size_t mpo_gp_score_ws_bytes(const MpoGpModel* model, int64_t m, int k) {
     if (!model || m <= 0 || k < 0 || k > MPO_TOPK_MAX) return 0;
-    int panel = 0;
-    const int plan = score_plan(model->n, model->dp, model->np16, &panel);
-    if (plan < 0) return 0;
-    size_t used = 0;
-    carve_score_ws(nullptr, m, k, &used, plan == 1 ? streamed_part_elems(model->dp, model->np16, panel, m) : 0);
-    return used + 256;
+    ScorePlan plan;
+    if (score_plan(nullptr, model, m, &plan)) return 0;
+    return carve_score_ws(nullptr, m, k, plan.part_elems).used + 256;
 }
 
-static int gp_score_impl(const MpoGpModel* model, const double* cand, int64_t m, double y_opt,
-                  double xi, double kappa, unsigned flags, int ei_positive, double* mu,
+// `who`: the entry point named in the plan's refusals and the workspace check.
+// ei_argmax (mpo_gp_ei_score): +EI instead of -EI in vals, and the top-1 index goes
+// to *ei_argmax through the tail of the workspace instead of topk_idx / topk_val.
+static int gp_score_impl(const char* who, const MpoGpModel* model, const double* cand, int64_t m, double y_opt,
+                  double xi, double kappa, unsigned flags, int64_t* ei_argmax, double* mu,
                   double* sd, double* vals, int k, int64_t* topk_idx, double* topk_val,
                   void* ws, size_t ws_bytes, hipStream_t s) {
     MPO_CHECK_ARG(model && cand, "mpo_gp_acq_score: null model/candidates");
     MPO_CHECK_ARG(m > 0, "mpo_gp_acq_score: m must be > 0");
     MPO_CHECK_ARG((flags & ~7u) == 0 && flags != 0, "mpo_gp_acq_score: bad flags %u", flags);
     MPO_CHECK_ARG(k >= 0 && k <= MPO_TOPK_MAX, "mpo_gp_acq_score: k=%d outside [0,%d]", k, MPO_TOPK_MAX);
-    MPO_CHECK_ARG(k == 0 || (topk_idx && topk_val), "mpo_gp_acq_score: topk outputs required for k>0");
+    MPO_CHECK_ARG(k == 0 || ei_argmax || (topk_idx && topk_val), "mpo_gp_acq_score: topk outputs required for k>0");
     MPO_CHECK_ARG(k > 0 || mu || sd || vals, "mpo_gp_acq_score: nothing to compute");
-    MPO_CHECK_ARG(ws && ws_bytes >= mpo_gp_score_ws_bytes(model, m, k), "mpo_gp_acq_score: workspace too small");
-    int panel = 0;
-    const int plan = score_plan(model->n, model->dp, model->np16, &panel);
-    if (plan < 0) {
-        mpo::set_error(plan == -MPO_ENOTSUP ? "mpo_gp_acq_score: n=%d exceeds the supported maximum of %d observations"
-                                            : "mpo_gp_acq_score: malformed model (n=%d) or MPO_GP_PANEL (a multiple of 16, >= 16; max n %d)",
-                       model->n, kScoreMaxN);
-        return -plan;
-    }
+    ScorePlan plan;
+    if (const int rc = score_plan(who, model, m, &plan)) return rc;
+    MPO_CHECK_ARG(ws && ws_bytes >= carve_score_ws(nullptr, m, k, plan.part_elems).used + 256,
+                  "%s: workspace too small", who);
+    const ScoreWs w = carve_score_ws(ws, m, k, plan.part_elems);
     const int64_t ntiles64 = (m + kBM - 1) / kBM;
     MPO_CHECK_ARG(ntiles64 < (1LL << 31), "mpo_gp_acq_score: too many candidates");
     const int ntiles = (int)ntiles64;
-    const ScoreWs w = carve_score_ws(ws, m, k, nullptr,
-                                     plan == 1 ? streamed_part_elems(model->dp, model->np16, panel, m) : 0);
-    long long* part_idx = w.part_idx;
-    double* part_val = w.part_val;
-    long long* mid_idx = w.mid_idx;
-    double* mid_val = w.mid_val;
+    if (ei_argmax) {
+        topk_idx = reinterpret_cast<int64_t*>(w.tail_idx);
+        topk_val = w.tail_val;
+    }
 
-    ScoreArgs a;
-    a.n = model->n;
-    a.np16 = model->np16;
-    a.T = model->np16 / 16;
-    a.d = model->d;
-    a.amp = model->amp;
-    a.y_mean = model->y_mean;
-    a.y_std = model->y_std;
-    a.xs = model->xs;
-    a.xb = model->xb;
-    a.xb_ok = model->xb ? model->xb + (size_t)(model->np16 + 32) * model->dp : nullptr;
-    a.ls = model->ls;
-    a.alpha = model->alpha;
-    a.wfrag = model->wfrag;
-    a.wmeta = model->wmeta;
+    ScoreArgs a = model_score_args(*model);
     a.cand = cand;
     a.m = m;
     a.y_opt = y_opt;
     a.xi = xi;
     a.kappa = kappa;
     a.flags = flags;
-    a.ei_positive = ei_positive;
+    a.ei_positive = ei_argmax != nullptr;
     {
         const char* e = getenv("MPO_GP_DEBUG");
         a.dbg = e ? atoi(e) : 0;
@@ -1977,28 +1946,28 @@ static int gp_score_impl(const MpoGpModel* model, const double* cand, int64_t m,
     a.sd = sd;
     a.vals = vals;
     a.k = k;
-    a.part_idx = part_idx;
-    a.part_val = part_val;
-    a.mq = w.mq;   // FIN: the workgroup's own rows, finished inside the scoring kernel
-    a.panel = panel;
+    a.part_idx = w.part_idx;
+    a.part_val = w.part_val;
+    a.mq = w.mq;   // the workgroup's own rows, finished inside the scoring kernel
+    a.panel = plan.panel;
     a.part = w.part;
     int grid = 0;
-    if (plan == 1) {
-        MPO_HIP(launch_streamed_dp(model->dp, model->d, a, ntiles, s, &grid));
-    } else {
-        const size_t lds = score_lds_bytes(model->dp, model->np16);
-        MPO_HIP(launch_score_dp(model->dp, model->d, a, ntiles, lds, s, /*fin=*/true, &grid));
-    }
+    MPO_HIP(launch_scoring(model->dp, model->d, plan, a, ntiles, s, /*fin=*/true, &grid));
     const int nparts = 4 * grid;
     if (k > 0) {
         // stage 1: G groups of ~64 wave-lists each; stage 2: one list
         const int chunk = std::max(64, (nparts + kMergeGroups - 1) / kMergeGroups);
         const int G = (nparts + chunk - 1) / chunk;
-        hipLaunchKernelGGL(topk_merge_kernel, dim3(G, 3), dim3(256), 0, s, part_idx, part_val, nparts, chunk, k,
-                           flags, mid_idx, mid_val, k, 0);
+        hipLaunchKernelGGL(topk_merge_kernel, dim3(G, 3), dim3(256), 0, s, w.part_idx, w.part_val, nparts, chunk, k,
+                           flags, w.mid_idx, w.mid_val, k, 0);
         MPO_LAUNCH_CHECK();
-        hipLaunchKernelGGL(topk_merge_kernel, dim3(1, 3), dim3(256), 0, s, mid_idx, mid_val, G, G, k, flags,
+        hipLaunchKernelGGL(topk_merge_kernel, dim3(1, 3), dim3(256), 0, s, w.mid_idx, w.mid_val, G, G, k, flags,
                            reinterpret_cast<long long*>(topk_idx), topk_val, k, 1);
+        MPO_LAUNCH_CHECK();
+    }
+    if (ei_argmax) {
+        hipLaunchKernelGGL(argmax_from_topk_kernel, dim3(1), dim3(1), 0, s, w.tail_idx,
+                           reinterpret_cast<long long*>(ei_argmax));
         MPO_LAUNCH_CHECK();
     }
     return MPO_OK;
@@ -2006,15 +1975,17 @@ static int gp_score_impl(const MpoGpModel* model, const double* cand, int64_t m,
 
 int mpo_gp_score_path(const MpoGpModel* model) {
     if (!model) return -MPO_EINVAL;
-    return score_plan(model->n, model->dp, model->np16, nullptr);
+    ScorePlan plan;
+    const int rc = score_plan(nullptr, model, 1, &plan);
+    return rc ? -rc : plan.path;
 }
 
 int mpo_gp_acq_score(const MpoGpModel* model, const double* cand, int64_t m, double y_opt, double xi,
                      double kappa, unsigned flags, double* mu, double* sd, double* vals, int k,
                      int64_t* topk_idx, double* topk_val, void* ws, size_t ws_bytes, void* stream) {
     MPO_GUARD_BEGIN
-    return gp_score_impl(model, cand, m, y_opt, xi, kappa, flags, 0, mu, sd, vals, k, topk_idx, topk_val, ws,
-                         ws_bytes, static_cast<hipStream_t>(stream));
+    return gp_score_impl("mpo_gp_acq_score", model, cand, m, y_opt, xi, kappa, flags, nullptr, mu, sd, vals, k, topk_idx,
+                         topk_val, ws, ws_bytes, static_cast<hipStream_t>(stream));
     MPO_GUARD_END
 }
 
@@ -2024,23 +1995,8 @@ int mpo_gp_ei_score(const MpoGpModel* model, const double* cand, int64_t m, doub
     MPO_GUARD_BEGIN
     MPO_CHECK_ARG(argmax, "mpo_gp_ei_score: null argmax");
     MPO_CHECK_ARG(model && m > 0, "mpo_gp_ei_score: null model or m <= 0");
-    if (model->n > kScoreMaxN) {
-        mpo::set_error("mpo_gp_ei_score: n=%d exceeds the supported maximum of %d observations", model->n, kScoreMaxN);
-        return MPO_ENOTSUP;
-    }
-    MPO_CHECK_ARG(mpo_gp_score_ws_bytes(model, m, 1) != 0, "mpo_gp_ei_score: malformed model or MPO_GP_PANEL");
-    MPO_CHECK_ARG(ws_bytes >= mpo_gp_score_ws_bytes(model, m, 1), "mpo_gp_ei_score: workspace too small");
-    // top-1 of -EI lands in the tail of the workspace the score call does not use
-    const ScoreWs w = carve_score_ws(ws, m, 1, nullptr);
-    long long* tidx = w.tail_idx;
-    double* tval = w.tail_val;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = gp_score_impl(model, cand, m, y_opt, xi, 1.96, MPO_ACQ_EI, 1, mu, sd, ei, 1,
-                           reinterpret_cast<int64_t*>(tidx), tval, ws, ws_bytes, s);
-    if (rc) return rc;
-    hipLaunchKernelGGL(argmax_from_topk_kernel, dim3(1), dim3(1), 0, s, tidx, reinterpret_cast<long long*>(argmax));
-    MPO_LAUNCH_CHECK();
-    return MPO_OK;
+    return gp_score_impl("mpo_gp_ei_score", model, cand, m, y_opt, xi, 1.96, MPO_ACQ_EI, argmax, mu, sd, ei, 1, nullptr,
+                         nullptr, ws, ws_bytes, static_cast<hipStream_t>(stream));
     MPO_GUARD_END
 }
 

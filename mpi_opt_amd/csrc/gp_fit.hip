@@ -42,7 +42,6 @@ namespace {
 
 constexpr int kFitThreads = 1024;
 constexpr int kFitWaves = kFitThreads / 64;
-constexpr int kFitMaxN = 2048;
 constexpr int kFitLdsMaxN = 200;  // 200*201/2 doubles = 160800 B of the 163840 B LDS
 constexpr double kSqrt5 = 2.236067977499789696409173668731276235;
 constexpr double kLog2Pi = 1.837877066409345483560659472811235280;
@@ -1636,7 +1635,7 @@ inline int fit_dp(int d) {
 // the split sweep: n > kSplitMinN (MPO_FIT_KERNEL=split forces it for n > 16)
 inline bool use_split(int n) {
     const char* e = getenv("MPO_FIT_KERNEL");
-    if (e && std::string(e) == "split") return n > 16 && n <= kFitMaxN;
+    if (e && std::string(e) == "split") return n > 16 && n <= mpo::kMaxObs;
     if (e && std::string(e) == "panel" && n <= kFitLdsMaxN) return false;
     return n > kSplitMinN;
 }
@@ -1663,7 +1662,7 @@ namespace mpo {
 
 bool lml_groupable(int n, int d) {
     const int dp = fit_dp(d);
-    return dp > 0 && n > 0 && n <= kFitMaxN && fit_fused_split(n, dp);
+    return dp > 0 && n > 0 && n <= mpo::kMaxObs && fit_fused_split(n, dp);
 }
 
 int lml_launch_rounds(const LmlRound* r, int count, hipStream_t s) {
@@ -1685,7 +1684,7 @@ int lml_launch_rounds(const LmlRound* r, int count, hipStream_t s) {
 extern "C" {
 
 size_t mpo_gp_lml_ws_bytes(int n, int d, int batch) {
-    if (n <= 0 || n > kFitMaxN || fit_dp(d) < 0 || batch <= 0) return 0;
+    if (n <= 0 || n > mpo::kMaxObs || fit_dp(d) < 0 || batch <= 0) return 0;
     const long long per = std::max(fit_ws_doubles(n, d, n <= kFitLdsMaxN), ss_ws_doubles(n, d));
     return ((size_t)per * batch + (size_t)batch * kPairGroups * 34) * sizeof(double) + 256;   // + pair partials
 }
@@ -1706,8 +1705,8 @@ static int lml_grad_impl(const double* X, const double* y_norm, int n, int d, co
     MPO_CHECK_ARG(X && y_norm && theta && lml && grad && info && ws, "mpo_gp_lml_grad: null pointer");
     MPO_CHECK_ARG(n > 0 && d > 0 && batch > 0, "mpo_gp_lml_grad: bad shape n=%d d=%d batch=%d", n, d, batch);
     const int dp = fit_dp(d);
-    if (dp < 0 || n > kFitMaxN) {
-        mpo::set_error("mpo_gp_lml_grad: n=%d d=%d outside n<=%d, d<=32", n, d, kFitMaxN);
+    if (dp < 0 || n > mpo::kMaxObs) {
+        mpo::set_error("mpo_gp_lml_grad: n=%d d=%d outside n<=%d, d<=32", n, d, mpo::kMaxObs);
         return MPO_ENOTSUP;
     }
     MPO_CHECK_ARG(ws_bytes >= mpo_gp_lml_ws_bytes(n, d, batch), "mpo_gp_lml_grad: workspace too small (%zu < %zu)",

@@ -20,6 +20,10 @@ namespace mpo {
 void set_error(const char* fmt, ...);
 void clear_error();
 
+// The most observations a GP may hold: the refit (gp_fit.hip) and the posterior /
+// scoring entry points (gp.hip) refuse more with MPO_ENOTSUP.
+constexpr int kMaxObs = 2048;
+
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Carve consecutive 256-B aligned regions out of a caller workspace.

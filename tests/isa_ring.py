@@ -1,8 +1,9 @@
-"""ISA check of the EI kernel's asm-load ring (test infrastructure).
+"""ISA check of the scoring kernels' asm-load rings (test infrastructure).
 
-``gp_score_kernel`` streams its B fragments through ``global_load_dwordx2``
+``gp_score_kernel`` (two-group ring) and ``gp_score_streamed_kernel``
+(three-group ring) stream their B fragments through ``global_load_dwordx2``
 issued from inline asm with an ``"=v"`` output and explicit ``s_waitcnt vmcnt``
-ties (mpi_opt_amd/csrc/gp.hip, MPO_LD / MPO_EI_GROUP).  The compiler believes
+ties (mpi_opt_amd/csrc/gp.hip, MPO_LD4 / MPO_EI_GROUP / MPO_ST_GROUP).  The compiler believes
 such a destination is written when the load issues, so nothing in the source
 stops it from reading, copying or reusing that register before the matching
 wait -- a hazard only the generated code can rule out.

@@ -1,10 +1,12 @@
-"""The EI kernel's asm-load ring is hazard-free in the code the compiler
-generated: every spill-free ``gp_score_kernel`` instance in
-libmpo.so's gfx950 code objects is checked instruction by instruction by
-tests/isa_ring.py -- no instruction reads, writes or copies a VGPR whose
+"""The scoring kernels' asm-load rings are hazard-free in the code the compiler
+generated: every spill-free ``gp_score_kernel`` instance
+(two-group ring) and every ``gp_score_streamed_kernel`` instance (three-group
+ring) in libmpo.so's gfx950 code objects is checked instruction by instruction
+by tests/isa_ring.py -- no instruction reads, writes or copies a VGPR whose
 ``global_load_dwordx2`` has not been retired by an ``s_waitcnt vmcnt`` on any
 control-flow path.  Instances that spill are refused at launch
-(``launch_score`` / ``spill_free`` in gp.hip) and are listed, not run.  CPU only."""
+(``launch_looped`` / ``spill_free`` in gp.hip) and are listed, not run.  CPU only."""
+import functools
 import os
 import re
 
@@ -34,22 +36,42 @@ def test_checker_flags_an_early_read_and_accepts_the_wait():
     assert R.check_function(loop)
 
 
+@functools.lru_cache(maxsize=None)
+def _functions():
+    """libmpo.so's gfx950 functions, disassembled once for both kernel tests."""
+    funcs = {}
+    for co in R.gfx950_code_objects(LIB):
+        funcs.update(R.functions(R.disassemble(co)))
+    return funcs
+
+
+def _scan(kernel):
+    """{instance: (spills, ring loads, hazards)} of the functions whose name contains ``kernel``."""
+    return {name: (any(i[1].startswith("scratch_") for i in insns),
+                   sum(1 for i in insns if i[1] == "global_load_dwordx2"), R.check_function(insns))
+            for name, insns in _functions().items() if kernel in name}
+
+
+@pytest.mark.skipif(not os.path.exists(LIB), reason="libmpo.so not built")
+def test_gp_score_streamed_kernel_ring_is_hazard_free():
+    res = _scan("gp_score_streamed_kernel")
+    assert len(res) == 7, sorted(res)                # one per (DP, D)
+    for name, (spills, ring, hazards) in res.items():
+        assert not spills, name                      # launch_looped would refuse it
+        assert ring >= 12, name                      # three groups of four loads
+        assert hazards == [], (name, hazards[:4])
+
+
 @pytest.mark.skipif(not os.path.exists(LIB), reason="libmpo.so not built")
 def test_gp_score_kernel_ring_is_hazard_free():
-    res = {}
-    for co in R.gfx950_code_objects(LIB):
-        for name, insns in R.functions(R.disassemble(co)).items():
-            if "gp_score_kernel" in name:
-                spills = any(i[1].startswith("scratch_") for i in insns)
-                ring = sum(1 for i in insns if i[1] == "global_load_dwordx2")
-                res[name] = (spills, ring, R.check_function(insns))
+    res = _scan("gp_score_kernel")
     assert len(res) >= 48
     groups = {}
     for name, (spills, ring, hazards) in res.items():
         dp, d, occ, md, fin = (int(v) for v in re.findall(r"Li(\d+)E", name.split("gp_score_kernel")[1])[:5])
         groups.setdefault((dp, d, md, fin), []).append((occ, spills, ring, hazards, name))
     for key, variants in groups.items():
-        # launch_score runs the highest-occupancy variant that does not spill
+        # resident_kernel_occ picks the highest-occupancy variant that does not spill
         launched = max((v for v in variants if not v[1]), default=None)
         assert launched is not None, key
         for occ, spills, ring, hazards, name in variants:
