@@ -337,6 +337,29 @@ int mpo_pop_train_step(void* handle, const float* x, const int32_t* labels, cons
 int mpo_pop_eval_step(void* handle, const float* x, const int32_t* labels, const int32_t* order,
                       int64_t order_stride, int64_t row0, float* loss_sum, int32_t* correct, void* stream);
 
+/* Retire / re-activate members (a population whose members stop early, option3's
+ * --early-stopping / --target-metric handed to MPIKFoldManager, process_block.py:83-90,
+ * stops paying for them).  active: HOST array of n_members bytes, non-zero = the member
+ * takes part in the following mpo_pop_train_step / mpo_pop_eval_step calls.  Every
+ * member is active after mpo_pop_create; any mask may follow any other (a member may
+ * come back), the current mask again is a no-op.
+ * A retired member costs no kernel work: the work lists are rebuilt from the active
+ * members' items (bucketed as a plan of those members alone) into the same `tables`
+ * region, whose size and every layout (mpo_pop_sizes, mpo_pop_param_layout,
+ * mpo_pop_act_layout) do not change.  Its parameters, gradients, Adam m / v and
+ * activations are not written, nor its loss_out / loss_sum / correct entries.  An
+ * active member's bits are those of the same steps with nobody retired.  With every
+ * member retired a step returns MPO_OK and launches nothing.
+ * Before mpo_pop_bind the call only replans (stream unused); after it the tables are
+ * uploaded on `stream`, which must be the stream the steps run on, and the call waits
+ * for that stream.  NOT capturable; a hipGraph captured before the call replays the
+ * old work lists and grid sizes and must be re-captured. */
+int mpo_pop_set_active(void* handle, const uint8_t* active, void* stream);
+/* Work of one mpo_pop_train_step under the current mask (host arithmetic only):
+ * workgroups over all its launches, and the launches.  Equal to those of a plan
+ * created from the active members' specs alone; 0 and 0 with every member retired. */
+int mpo_pop_step_work(const void* handle, int64_t* items, int64_t* launches);
+
 /* Diagnostics: per-phase device milliseconds accumulated over the steps run
  * since the last reset, as "phase ms\n" lines into buf (cap bytes).  Only
  * populated when the plan was created with MPO_POP_PROFILE=1 in the
@@ -363,7 +386,9 @@ typedef struct MpoDnArch {
 typedef struct MpoDnSizes {
     int64_t n_params;     /* floats per member in the parameter arena (also grads, adam m, v) */
     int64_t n_state;      /* floats per member of BN moving statistics                         */
-    int64_t act_floats;   /* floats in the activation arena (all members)                      */
+    int64_t act_floats;   /* floats in the activation arena (all members); ends with the per-member
+                             lr table and the active member table of mpo_dn_set_active (int32
+                             [n_members], each rounded up to 64 floats)                        */
     int32_t n_members;
     int32_t batch;
     int32_t n_layers;
@@ -396,8 +421,25 @@ int mpo_dn_train_step(void* handle, const float* x, const int32_t* labels, const
  * sum of per-sample CE, correct[member] += argmax hits. */
 int mpo_dn_eval_step(void* handle, const float* x, const int32_t* labels, const int32_t* order,
                      int64_t order_stride, int64_t row0, float* loss_sum, int32_t* correct, void* stream);
-/* out[member] = 1e-4 * sum of squared parameters (Keras adds it to val_loss). */
+/* out[member] = 1e-4 * sum of squared parameters (Keras adds it to val_loss).
+ * Written for every member, retired or not. */
 int mpo_dn_penalty(void* handle, float* out, void* stream);
+/* mpo_pop_set_active for the DenseNet population, same semantics: active is a HOST
+ * array of n_members bytes; the following mpo_dn_train_step / mpo_dn_eval_step calls
+ * launch grids over the active members only, each workgroup reading its member from a
+ * device table of active indices in the activation arena (act_floats grew by that table
+ * only).  A retired member's parameters, gradients, Adam m / v, BN state and
+ * activations are not written, nor its loss_out / loss_sum / correct entries.  The work
+ * splits stay sized for the nominal population, so an active member's bits do not
+ * change; with every member retired a step returns MPO_OK and launches nothing.
+ * Before mpo_dn_bind it only replans; after it the table is uploaded on `stream` (the
+ * stream the steps run on) and the call waits for that stream, as mpo_dn_bind does.
+ * NOT capturable; a hipGraph captured before the call replays the old grid sizes and
+ * must be re-captured. */
+int mpo_dn_set_active(void* handle, const uint8_t* active, void* stream);
+/* Workgroups and launches of one mpo_dn_train_step under the current mask (host
+ * arithmetic only): those of a plan of as many members as are active. */
+int mpo_dn_step_work(const void* handle, int64_t* workgroups, int64_t* launches);
 
 /* k-fold index gather: out[r][:] = X[idx[r]][:] (the fold split
  * that mpi_learn does with per-fold communicators becomes an index gather). */

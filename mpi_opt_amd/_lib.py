@@ -116,6 +116,8 @@ SIGNATURES = {
     "mpo_pop_bind": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "mpo_pop_train_step": (_I, [_P, _P, _P, _P, _I64, _I64, ctypes.c_int32, _P, _P]),
     "mpo_pop_eval_step": (_I, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
+    "mpo_pop_set_active": (_I, [_P, _P, _P]),
+    "mpo_pop_step_work": (_I, [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "mpo_pop_profile": (_I, [_P, _P, _SZ, _I]),
     "mpo_dn_create": (_I, [ctypes.POINTER(MpoDnArch), _I, _I, ctypes.POINTER(ctypes.c_void_p)]),
     "mpo_dn_destroy": (_I, [_P]),
@@ -125,6 +127,8 @@ SIGNATURES = {
     "mpo_dn_train_step": (_I, [_P, _P, _P, _P, _I64, _I64, ctypes.c_int32, _P, _P]),
     "mpo_dn_eval_step": (_I, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "mpo_dn_penalty": (_I, [_P, _P, _P]),
+    "mpo_dn_set_active": (_I, [_P, _P, _P]),
+    "mpo_dn_step_work": (_I, [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
     "mpo_kfold_gather": (_I, [_P, _P, _I64, _I, _P, _P]),
 }
 

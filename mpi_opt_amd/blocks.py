@@ -61,7 +61,7 @@ class TrialEvaluator:
 
     def __init__(self, model_provider, x, y, n_fold=1, epochs=10, batch=100, lr=1e-3, device=None,
                  history_dir=None, init_seed=0, holdout=None, progress=None, loss="binary_crossentropy",
-                 optimizer="adam", stopping=None):
+                 optimizer="adam", stopping=None, retire_stopped=True):
         self.model_provider = model_provider
         self.x, self.y = x, y
         self.n_fold, self.epochs, self.batch, self.lr = n_fold, epochs, batch, lr
@@ -70,6 +70,10 @@ class TrialEvaluator:
         # (categorical_crossentropy + Adam, base_model.py:71-72)
         self.loss, self.optimizer = loss, optimizer
         self.stopping = stopping    # stopping.StopRule: --early-stopping / --target-metric (process_block.py:83-90)
+        # members a rule stopped leave their population's later steps (fit_folds retire_stopped): the
+        # histories end at epochs_run either way, so FOMs and histories are the same with False
+        self.retire_stopped = retire_stopped
+        self.member_epochs_skipped = 0   # epochs retired members sat out while their population trained on
         self.device = device
         self.history_dir = history_dir
         self.init_seed = init_seed
@@ -138,7 +142,7 @@ class TrialEvaluator:
         eng = PopulationEngine(specs, batch=self.batch, device=self.device, init=init)
         return self._histories(units, eng.fit_folds(self.x, self.y, folds, self.n_fold, self.epochs,
                                                       holdout=self.holdout, progress=self._epoch_cb(len(units)),
-                                                      stopping=self.stopping))
+                                                      stopping=self.stopping, retire_stopped=self.retire_stopped))
 
     def _epoch_cb(self, members):
         if self.progress is None:
@@ -160,10 +164,12 @@ class TrialEvaluator:
         pop = DenseNetPopulation(arch, lrs, batch=self.batch, device=self.device, init=init)
         return self._histories(units, pop.fit_folds(self.x, self.y, folds, self.n_fold, self.epochs,
                                                       holdout=self.holdout, progress=self._epoch_cb(len(units)),
-                                                      stopping=self.stopping))
+                                                      stopping=self.stopping, retire_stopped=self.retire_stopped))
 
-    @staticmethod
-    def _histories(units, hist):
+    def _histories(self, units, hist):
+        if self.retire_stopped and self.stopping is not None:
+            run = np.asarray(hist["epochs_run"])
+            self.member_epochs_skipped += int((run.max() - run).sum())   # the population ran max(epochs_run) epochs
         out = {}
         for i, (t, f, _, _) in enumerate(units):
             e = int(hist["epochs_run"][i])         # a stopped member's history ends at its stopping epoch

@@ -1541,6 +1541,20 @@ struct Plan {
     Bucketed bw1, bw2;
     std::vector<GemmItem> d1f, d2f, d2w, d2d, d1w, d1d;
     std::vector<MItem> per_member, per_sample, colsum, wred, adam;
+    // Every member's work in creation order, as build_plan generated it, with what the
+    // bucketing needs (per-member LDS bytes per op, the occmerge / xcd knobs).  The
+    // lists above are the ACTIVE members' (mpo_pop_set_active): apply_mask filters
+    // these by item.member and buckets / deals the result as for a fresh plan.
+    struct FullLists {
+        std::vector<ConvItem> conv1, conv2, dgrad, dgf;
+        std::vector<WgItem> wg1, wg2;
+        std::vector<GemmItem> d1f, d2f, d2w, d2d, d1w, d1d;
+        std::vector<MItem> per_member, per_sample, colsum, adam;
+    } full;
+    std::vector<size_t> L1, L2, LD, LDF, LW1, LW2;
+    int occmerge = 2, xcd = 4;
+    std::vector<uint8_t> active;   // [n] 0 / 1
+    int na = 0;                    // active members: per_member.size()
     int adam_chunk = 8192;
     int wred_per_block = 4096, wred_blocks = 1;
     // device tables
@@ -1688,10 +1702,132 @@ int wg_mt(int Kw, int mg) {
     return std::max(1, std::min(kWgMaxMT, (tiles + kWgWaves - 1) / kWgWaves));
 }
 
+template <class T>
+void keep_active(const std::vector<T>& full, const std::vector<uint8_t>& active, std::vector<T>& out) {
+    out.clear();
+    for (const T& x : full)
+        if (active[x.member]) out.push_back(x);
+}
+
+// The active members' work lists from the full ones (P.active), bucketed and dealt
+// exactly as a plan created from the active specs alone would have them: the
+// filtered lists keep the creation order, and the segmenting only looks at each
+// item's member.  Items keep their original member indices (the Member table and
+// the arenas do not move).  No arithmetic depends on the segmenting or on the
+// item order, so an active member's bits do not change.
+void apply_mask(Plan& P) {
+    const Plan::FullLists& F = P.full;
+    keep_active(F.conv1, P.active, P.conv1);
+    keep_active(F.conv2, P.active, P.conv2);
+    keep_active(F.dgrad, P.active, P.dgrad);
+    keep_active(F.dgf, P.active, P.dgf);
+    keep_active(F.wg1, P.active, P.wg1);
+    keep_active(F.wg2, P.active, P.wg2);
+    keep_active(F.d1f, P.active, P.d1f);
+    keep_active(F.d2f, P.active, P.d2f);
+    keep_active(F.d2w, P.active, P.d2w);
+    keep_active(F.d2d, P.active, P.d2d);
+    keep_active(F.d1w, P.active, P.d1w);
+    keep_active(F.d1d, P.active, P.d1d);
+    keep_active(F.per_member, P.active, P.per_member);
+    keep_active(F.per_sample, P.active, P.per_sample);
+    keep_active(F.colsum, P.active, P.colsum);
+    keep_active(F.adam, P.active, P.adam);
+    P.na = (int)P.per_member.size();
+    // slab reductions, addressed by halves: conv2 slabs are items [0, na) (reduced on
+    // the side stream), conv1 slabs items [na, 2 na)
+    P.wred.clear();
+    for (const MItem& it : P.per_member) P.wred.push_back({it.member, 1});
+    for (const MItem& it : P.per_member) P.wred.push_back({it.member, 0});
+    long long wmax = 1;
+    for (const MItem& it : P.per_member) {
+        const Member& m = P.mem[it.member];
+        wmax = std::max(wmax, (long long)m.k * m.k * m.F * m.F + m.F);
+    }
+    P.wred_blocks = (int)((wmax + P.wred_per_block - 1) / P.wred_per_block);
+    bucket_segs(P.conv1, P.bc1, P.mem, P.L1, P.occmerge);
+    bucket_segs(P.conv2, P.bc2, P.mem, P.L2, P.occmerge);
+    bucket_segs(P.dgrad, P.bdg, P.mem, P.LD, P.occmerge);
+    bucket_segs(P.dgf, P.bdf, P.mem, P.LDF, P.occmerge);
+    bucket_segs(P.wg1, P.bw1, P.mem, P.LW1, P.occmerge);
+    bucket_segs(P.wg2, P.bw2, P.mem, P.LW2, P.occmerge);
+    xcd_deal(P.conv1, P.bc1, P.xcd);
+    xcd_deal(P.conv2, P.bc2, P.xcd);
+    xcd_deal(P.dgrad, P.bdg, P.xcd);
+    xcd_deal(P.dgf, P.bdf, P.xcd);
+    xcd_deal(P.wg1, P.bw1, P.xcd);
+    xcd_deal(P.wg2, P.bw2, P.xcd);
+}
+
+// Serialise the tables for one device upload.  layout = true (mpo_pop_create, every
+// member active) fixes each table's offset and the size of the region; later calls
+// rewrite the same region in place: an active list is never longer than the full one.
+void write_tables(Plan& P, bool layout) {
+    size_t off = 0;
+    auto put = [&](size_t& slot, const void* src, size_t bytes) {
+        if (layout) {
+            off = mpo::align_up(off, 256);
+            slot = off;
+            off += bytes;
+            P.host_tables.resize(off);
+        }
+        if (bytes) std::copy_n(static_cast<const char*>(src), bytes, P.host_tables.data() + slot);
+    };
+    put(P.off_mem, P.mem.data(), P.mem.size() * sizeof(Member));
+    put(P.off_conv1, P.conv1.data(), P.conv1.size() * sizeof(ConvItem));
+    put(P.off_conv2, P.conv2.data(), P.conv2.size() * sizeof(ConvItem));
+    put(P.off_dgrad, P.dgrad.data(), P.dgrad.size() * sizeof(ConvItem));
+    put(P.off_dgf, P.dgf.data(), P.dgf.size() * sizeof(ConvItem));
+    put(P.off_wg1, P.wg1.data(), P.wg1.size() * sizeof(WgItem));
+    put(P.off_wg2, P.wg2.data(), P.wg2.size() * sizeof(WgItem));
+    put(P.off_d1f, P.d1f.data(), P.d1f.size() * sizeof(GemmItem));
+    put(P.off_d2f, P.d2f.data(), P.d2f.size() * sizeof(GemmItem));
+    put(P.off_d2w, P.d2w.data(), P.d2w.size() * sizeof(GemmItem));
+    put(P.off_d2d, P.d2d.data(), P.d2d.size() * sizeof(GemmItem));
+    put(P.off_d1w, P.d1w.data(), P.d1w.size() * sizeof(GemmItem));
+    put(P.off_d1d, P.d1d.data(), P.d1d.size() * sizeof(GemmItem));
+    put(P.off_pm, P.per_member.data(), P.per_member.size() * sizeof(MItem));
+    put(P.off_ps, P.per_sample.data(), P.per_sample.size() * sizeof(MItem));
+    put(P.off_cs, P.colsum.data(), P.colsum.size() * sizeof(MItem));
+    put(P.off_wr, P.wred.data(), P.wred.size() * sizeof(MItem));
+    put(P.off_adam, P.adam.data(), P.adam.size() * sizeof(MItem));
+    if (layout) {
+        P.table_bytes = mpo::align_up(off, 256);
+        P.host_tables.resize(P.table_bytes);
+    }
+}
+
+// Workgroups and launches of one train step under the current mask, as
+// mpo_pop_train_step enqueues them (the side-stream form unless the plan is serial).
+void step_work(const Plan& P, long long* items, long long* launches) {
+    long long it = 0, ln = 0;
+    if (P.na > 0) {
+        auto one = [&](long long blocks) { if (blocks > 0) { it += blocks; ++ln; } };
+        auto segs = [&](const Bucketed& bk) { for (const Seg& sg : bk.segs) one(sg.end - sg.begin); };
+        one(64LL * P.na);                                  // flip_w2
+        segs(P.bc1); segs(P.bc2);
+        one((long long)P.per_sample.size());               // pool_fwd
+        one((long long)P.d1f.size()); one((long long)P.d2f.size());
+        one(P.na);                                         // softmax_bce
+        one((long long)P.d2w.size()); one((long long)P.d2d.size());
+        one((long long)P.d1w.size()); one((long long)P.d1d.size());
+        one((long long)P.per_sample.size());               // pool_bwd
+        segs(P.bdf); segs(P.bdg); segs(P.bw2); segs(P.bw1);
+        if (P.side.enabled && !P.timer.on) { one((long long)P.wred_blocks * P.na); one((long long)P.wred_blocks * P.na); }
+        else one(2LL * P.wred_blocks * P.na);              // wgrad_reduce
+        one((long long)P.colsum.size());
+        one((long long)P.adam.size());
+    }
+    *items = it;
+    *launches = ln;
+}
+
 int build_plan(Plan& P, const MpoCnnSpec* specs, int n, int B) {
     P.n = n;
     P.B = B;
     P.mem.resize(n);
+    P.active.assign(n, 1);
+    Plan::FullLists& FL = P.full;
     long long po = 0, ao = 0;
     auto palloc = [&](long long cnt) { long long o = po; po += (cnt + 63) / 64 * 64; return o; };
     auto aalloc = [&](long long cnt) { long long o = ao; ao += (cnt + 63) / 64 * 64; return o; };
@@ -1774,7 +1910,8 @@ int build_plan(Plan& P, const MpoCnnSpec* specs, int n, int B) {
     // 37.13 / 37.08 ms per 320-member step, 3.95 -> 3.86 ms at 40, 1.633 -> 1.642 at 20 (24 and 36 alike)
     const int kc1 = plan_knob("conv_kb1", 30), kc2 = plan_knob("conv_kb2", 100);
     const int kdg = plan_knob("dg_kb", 78);
-    std::vector<size_t> L1(n), L2(n), LD(n), LDF(n), LW1(n), LW2(n);   // per-member LDS bytes per op
+    for (auto* v : {&P.L1, &P.L2, &P.LD, &P.LDF, &P.LW1, &P.LW2}) v->assign(n, 0);   // per-member LDS bytes per op
+    auto &L1 = P.L1, &L2 = P.L2, &LD = P.LD, &LDF = P.LDF, &LW1 = P.LW1, &LW2 = P.LW2;
     for (int i = 0; i < n; ++i) {
         const Member& m = P.mem[i];
         const int k = m.k, F = m.F, nt = m.nt;
@@ -1813,13 +1950,13 @@ int build_plan(Plan& P, const MpoCnnSpec* specs, int n, int B) {
         if (fwd_dg) ld = conv_lds_bytes(Rf + k - 1, Hp, F4, m.H1, k * k * F4, nt);
         L1[i] = l1; L2[i] = l2; LD[i] = ld; LDF[i] = ld;
         for (int b = 0; b < B; ++b) {
-            for (int y = 0; y < m.H1; y += R1) P.conv1.push_back({i, b, y, std::min(R1, m.H1 - y)});
-            for (int y = 0; y < m.H2; y += R2) P.conv2.push_back({i, b, y, std::min(R2, m.H2 - y)});
+            for (int y = 0; y < m.H1; y += R1) FL.conv1.push_back({i, b, y, std::min(R1, m.H1 - y)});
+            for (int y = 0; y < m.H2; y += R2) FL.conv2.push_back({i, b, y, std::min(R2, m.H2 - y)});
             if (fwd_dg)
-                for (int y = 0; y < m.H1; y += Rf) P.dgf.push_back({i, b, y, std::min(Rf, m.H1 - y)});
+                for (int y = 0; y < m.H1; y += Rf) FL.dgf.push_back({i, b, y, std::min(Rf, m.H1 - y)});
             else
-                for (int y = 0; y < m.H1; y += Rd) P.dgrad.push_back({i, b, y, std::min(Rd, m.H1 - y)});
-            P.per_sample.push_back({i, b});
+                for (int y = 0; y < m.H1; y += Rd) FL.dgrad.push_back({i, b, y, std::min(Rd, m.H1 - y)});
+            FL.per_sample.push_back({i, b});
         }
         P.lds_conv_max = std::max({P.lds_conv_max, l1, l2, ld});
         // wgrad items: (member, 512-row m-group, sample group)
@@ -1833,40 +1970,35 @@ int build_plan(Plan& P, const MpoCnnSpec* specs, int n, int B) {
         const int K2 = k * k * F, K1w = k * k;
         for (int g = 0; g < m.g2; ++g) {
             const int b0 = (int)((long long)B * g / m.g2), b1 = (int)((long long)B * (g + 1) / m.g2);
-            for (int mg = 0; mg * kWgRows <= K2; ++mg) P.wg2.push_back({i, mg, b0, b1, g, wg_mt(K2, mg)});
+            for (int mg = 0; mg * kWgRows <= K2; ++mg) FL.wg2.push_back({i, mg, b0, b1, g, wg_mt(K2, mg)});
         }
         // conv1_wgrad_kernel: every m-tile in one wave, MT bucketed to 1, 2, 4 or 7
         const int t1 = (K1w + 1 + 15) / 16, mt1 = t1 <= 1 ? 1 : t1 <= 2 ? 2 : t1 <= 4 ? 4 : 7;
         LW1[i] = (size_t)w1_lds_floats((B + m.g1 - 1) / m.g1, mt1, nt) * sizeof(float);
         for (int g = 0; g < m.g1; ++g) {
             const int b0 = (int)((long long)B * g / m.g1), b1 = (int)((long long)B * (g + 1) / m.g1);
-            P.wg1.push_back({i, 0, b0, b1, g, mt1});
+            FL.wg1.push_back({i, 0, b0, b1, g, mt1});
         }
         P.lds_wg_max = std::max({P.lds_wg_max, lw2, lw1});
         auto tiles = [&](std::vector<GemmItem>& v, int M, int N) {
             for (int m0 = 0; m0 < M; m0 += 64)
                 for (int n0 = 0; n0 < N; n0 += 64) v.push_back({i, m0, n0, 0});
         };
-        tiles(P.d1f, B, m.dense);
-        tiles(P.d2f, B, kClasses);
-        tiles(P.d2w, m.dense, kClasses);
-        tiles(P.d2d, B, m.dense);
-        tiles(P.d1w, m.K1, m.dense);
-        tiles(P.d1d, B, m.K1);
-        P.per_member.push_back({i, 0});
-        for (int c = 2; c < 4; ++c) P.colsum.push_back({i, c});
-        P.wred.push_back({i, 1});   // conv2 slabs: items [0, n) (reduced on the side stream)
+        tiles(FL.d1f, B, m.dense);
+        tiles(FL.d2f, B, kClasses);
+        tiles(FL.d2w, m.dense, kClasses);
+        tiles(FL.d2d, B, m.dense);
+        tiles(FL.d1w, m.K1, m.dense);
+        tiles(FL.d1d, B, m.K1);
+        FL.per_member.push_back({i, 0});
+        for (int c = 2; c < 4; ++c) FL.colsum.push_back({i, c});
         const long long np_ = m.pend - m.w1;
-        for (long long c = 0; c * P.adam_chunk < np_; ++c) P.adam.push_back({i, (int)c});
+        for (long long c = 0; c * P.adam_chunk < np_; ++c) FL.adam.push_back({i, (int)c});
     }
     if (P.lds_conv_max > 160 * 1024 || P.lds_wg_max > 160 * 1024) {
         mpo::set_error("mpo_pop_create: LDS plan exceeds 160 KiB (conv %zu, wgrad %zu)", P.lds_conv_max, P.lds_wg_max);
         return MPO_ENOTSUP;
     }
-    for (int i = 0; i < n; ++i) P.wred.push_back({i, 0});   // conv1 slabs: items [n, 2n)
-    long long wmax = 0;
-    for (auto& m : P.mem) wmax = std::max(wmax, (long long)m.k * m.k * m.F * m.F + m.F);
-    P.wred_blocks = (int)((wmax + P.wred_per_block - 1) / P.wred_per_block);
     // Small populations (a distributed shard, configs[0]) launch too few workgroups per occupancy class
     // to fill the chip.  Merging every class of an (NT, sub) bucket (mode 1) measured on MI355X
     // (profiles/r05/occmerge_o.log): 20 members 3.82 -> 3.52 ms, 40: 5.93 -> 5.70, 80: 10.94 -> 10.96,
@@ -1874,51 +2006,10 @@ int build_plan(Plan& P, const MpoCnnSpec* specs, int n, int B) {
     // short of one full wave (mode 2, the default): 20: 3.53, 40: 5.56-5.59, 80: 10.63-10.67,
     // 320: 36.81-36.95 (separate classes 36.87) -- profiles/r05/occmerge2_*.log.  The segmenting
     // changes no arithmetic.
-    const int occ = plan_knob("occmerge", 2);
-    bucket_segs(P.conv1, P.bc1, P.mem, L1, occ);
-    bucket_segs(P.conv2, P.bc2, P.mem, L2, occ);
-    bucket_segs(P.dgrad, P.bdg, P.mem, LD, occ);
-    bucket_segs(P.dgf, P.bdf, P.mem, LDF, occ);
-    bucket_segs(P.wg1, P.bw1, P.mem, LW1, occ);
-    bucket_segs(P.wg2, P.bw2, P.mem, LW2, occ);
-    const int xc = plan_knob("xcd", 4);
-    xcd_deal(P.conv1, P.bc1, xc);
-    xcd_deal(P.conv2, P.bc2, xc);
-    xcd_deal(P.dgrad, P.bdg, xc);
-    xcd_deal(P.dgf, P.bdf, xc);
-    xcd_deal(P.wg1, P.bw1, xc);
-    xcd_deal(P.wg2, P.bw2, xc);
-
-    // ---- serialise tables (one device upload)
-    size_t off = 0;
-    auto put = [&](const void* src, size_t bytes) {
-        off = mpo::align_up(off, 256);
-        const size_t o = off;
-        P.host_tables.resize(off + bytes);
-        if (bytes) std::copy_n(static_cast<const char*>(src), bytes, P.host_tables.data() + o);
-        off += bytes;
-        return o;
-    };
-    P.off_mem = put(P.mem.data(), P.mem.size() * sizeof(Member));
-    P.off_conv1 = put(P.conv1.data(), P.conv1.size() * sizeof(ConvItem));
-    P.off_conv2 = put(P.conv2.data(), P.conv2.size() * sizeof(ConvItem));
-    P.off_dgrad = put(P.dgrad.data(), P.dgrad.size() * sizeof(ConvItem));
-    P.off_dgf = put(P.dgf.data(), P.dgf.size() * sizeof(ConvItem));
-    P.off_wg1 = put(P.wg1.data(), P.wg1.size() * sizeof(WgItem));
-    P.off_wg2 = put(P.wg2.data(), P.wg2.size() * sizeof(WgItem));
-    P.off_d1f = put(P.d1f.data(), P.d1f.size() * sizeof(GemmItem));
-    P.off_d2f = put(P.d2f.data(), P.d2f.size() * sizeof(GemmItem));
-    P.off_d2w = put(P.d2w.data(), P.d2w.size() * sizeof(GemmItem));
-    P.off_d2d = put(P.d2d.data(), P.d2d.size() * sizeof(GemmItem));
-    P.off_d1w = put(P.d1w.data(), P.d1w.size() * sizeof(GemmItem));
-    P.off_d1d = put(P.d1d.data(), P.d1d.size() * sizeof(GemmItem));
-    P.off_pm = put(P.per_member.data(), P.per_member.size() * sizeof(MItem));
-    P.off_ps = put(P.per_sample.data(), P.per_sample.size() * sizeof(MItem));
-    P.off_cs = put(P.colsum.data(), P.colsum.size() * sizeof(MItem));
-    P.off_wr = put(P.wred.data(), P.wred.size() * sizeof(MItem));
-    P.off_adam = put(P.adam.data(), P.adam.size() * sizeof(MItem));
-    P.table_bytes = mpo::align_up(off, 256);
-    P.host_tables.resize(P.table_bytes);
+    P.occmerge = plan_knob("occmerge", 2);
+    P.xcd = plan_knob("xcd", 4);
+    apply_mask(P);
+    write_tables(P, true);
     return MPO_OK;
 }
 
@@ -2077,7 +2168,7 @@ StepArgs make_args(const Plan& P, const float* x, const int* labels, const int* 
 int forward(Plan& P, const StepArgs& a, hipStream_t s) {
     P.timer.mark("start", s);
     // padded / rotated weight copies for this step's convolutions
-    hipLaunchKernelGGL(flip_w2_kernel, dim3(64, (unsigned)P.n), dim3(256), 0, s, a, dev_table<MItem>(P, P.off_pm));
+    hipLaunchKernelGGL(flip_w2_kernel, dim3(64, (unsigned)P.na), dim3(256), 0, s, a, dev_table<MItem>(P, P.off_pm));
     MPO_LAUNCH_CHECK();
     P.timer.mark("flip_w2", s);
     MPO_HIP(launch_conv<CONV1_FWD>(P, a, P.off_conv1, P.bc1, s));
@@ -2095,7 +2186,7 @@ int forward(Plan& P, const StepArgs& a, hipStream_t s) {
     MPO_HIP(launch_dense<D1_FWD>(P, a, P.off_d1f, P.d1f.size(), s));
     MPO_HIP(launch_dense<D2_FWD>(P, a, P.off_d2f, P.d2f.size(), s));
     P.timer.mark("dense_fwd", s);
-    hipLaunchKernelGGL(softmax_bce_kernel, dim3((unsigned)P.n), dim3(256), 0, s, a, dev_table<MItem>(P, P.off_pm));
+    hipLaunchKernelGGL(softmax_bce_kernel, dim3((unsigned)P.na), dim3(256), 0, s, a, dev_table<MItem>(P, P.off_pm));
     MPO_LAUNCH_CHECK();
     P.timer.mark("softmax_bce", s);
     return MPO_OK;
@@ -2176,6 +2267,36 @@ int mpo_pop_bind(void* handle, float* params, float* grads, float* adam_m, float
     MPO_GUARD_END
 }
 
+int mpo_pop_set_active(void* handle, const uint8_t* active, void* stream) {
+    MPO_GUARD_BEGIN
+    MPO_CHECK_ARG(handle && active, "mpo_pop_set_active: null pointer");
+    Plan& P = *static_cast<Plan*>(handle);
+    bool same = true;
+    for (int i = 0; i < P.n; ++i) same = same && (active[i] != 0) == (P.active[i] != 0);
+    if (same) return MPO_OK;
+    for (int i = 0; i < P.n; ++i) P.active[i] = active[i] != 0;
+    apply_mask(P);
+    write_tables(P, false);
+    if (P.bound) {
+        // stream order puts the copy after the steps enqueued so far (their side streams
+        // have joined `stream`); the wait keeps host_tables ours to rewrite next time
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        MPO_HIP(hipMemcpyAsync(P.table_base, P.host_tables.data(), P.table_bytes, hipMemcpyHostToDevice, s));
+        MPO_HIP(hipStreamSynchronize(s));
+    }
+    return MPO_OK;
+    MPO_GUARD_END
+}
+
+int mpo_pop_step_work(const void* handle, int64_t* items, int64_t* launches) {
+    MPO_CHECK_ARG(handle && items && launches, "mpo_pop_step_work: null pointer");
+    long long it = 0, ln = 0;
+    step_work(*static_cast<const Plan*>(handle), &it, &ln);
+    *items = it;
+    *launches = ln;
+    return MPO_OK;
+}
+
 int mpo_pop_train_step(void* handle, const float* x, const int32_t* labels, const int32_t* order, int64_t order_stride,
                        int64_t row0, int32_t step, float* loss_out, void* stream) {
     MPO_GUARD_BEGIN
@@ -2183,6 +2304,7 @@ int mpo_pop_train_step(void* handle, const float* x, const int32_t* labels, cons
     Plan& P = *static_cast<Plan*>(handle);
     MPO_CHECK_ARG(P.bound, "mpo_pop_train_step: call mpo_pop_bind first");
     MPO_CHECK_ARG(step >= 0, "mpo_pop_train_step: step must be >= 0");
+    if (P.na == 0) return MPO_OK;   // every member retired: nothing to launch
     hipStream_t s = static_cast<hipStream_t>(stream);
     StepArgs a = make_args(P, x, labels, order, order_stride, row0, step, 1);
     a.loss_out = loss_out;
@@ -2194,7 +2316,7 @@ int mpo_pop_train_step(void* handle, const float* x, const int32_t* labels, cons
     // weight gradient, and s joins s2 before Adam.
     hipStream_t s2 = P.timer.on ? nullptr : P.side.get(s);
     const MItem* wred = dev_table<MItem>(P, P.off_wr);
-    const unsigned nm = (unsigned)P.n;
+    const unsigned nm = (unsigned)P.na;   // the wred halves: items [0, na) conv2, [na, 2 na) conv1
     if (s2) {
         MPO_HIP(P.side.fork(s, s2));                                        // dz3 ready
         MPO_HIP(launch_dense<D2_WGRAD>(P, a, P.off_d2w, P.d2w.size(), s2));
@@ -2265,6 +2387,7 @@ int mpo_pop_eval_step(void* handle, const float* x, const int32_t* labels, const
     MPO_CHECK_ARG(handle && x && labels && order && loss_sum && correct, "mpo_pop_eval_step: null pointer");
     Plan& P = *static_cast<Plan*>(handle);
     MPO_CHECK_ARG(P.bound, "mpo_pop_eval_step: call mpo_pop_bind first");
+    if (P.na == 0) return MPO_OK;
     StepArgs a = make_args(P, x, labels, order, order_stride, row0, 0, 0);
     a.loss_sum = loss_sum;
     a.correct = correct;

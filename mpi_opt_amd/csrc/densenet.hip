@@ -83,6 +83,7 @@ struct ConvArgs {
     const float* rx; long long rx_ms; int rx_ps;
     const float* rcoef; long long rcoef_ms;
     double* rpart; int rS;
+    const int* mmap;   // active member table (member_of)
 };
 
 struct WgArgs {
@@ -94,6 +95,7 @@ struct WgArgs {
     float* part; long long part_ms;                       // [G][Kw][N]
     int H, W, Cin, N, R, spg, B;
     int kw;        // dn_wgrad3: k-step interleave inside the workgroup (wg3_kw), 1 for dn_wgrad1
+    const int* mmap;   // active member table (member_of)
 };
 
 struct BnArgs {
@@ -110,7 +112,16 @@ struct BnArgs {
     int c0;        // dn_bn_stats reads channels [c0, Cin) (the growth slices new since the previous site)
     int prev;      // dn_bn_coef adds the previous site's totals (tot) to the slice partials
     double* tot;   // folded (sum, sum of squares) per (member, h): [n][H][2]
+    const int* mmap;   // active member table (member_of)
 };
+
+// The member a workgroup works for: entry `slot` (the block index along the launch's
+// member axis) of the device table of active members (mpo_dn_set_active).  Grids span
+// the active count; every address uses the member's real index, so the table is the
+// identity while nobody is retired.  One value per workgroup: kept in an SGPR.
+__device__ __forceinline__ int member_of(const int* __restrict__ mmap, unsigned slot) {
+    return __builtin_amdgcn_readfirstlane(mmap[slot]);
+}
 
 // ---- shared reductions -----------------------------------------------------------
 // e = q*C + c walked by a fixed step (one division per thread, not per element)
@@ -275,7 +286,7 @@ template <int KS, int NT>
 __global__ __launch_bounds__(256) void dn_conv_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int P = (KS - 1) / 2;
-    const int m = blockIdx.z, b = blockIdx.y, y0 = blockIdx.x * a.R;
+    const int m = member_of(a.mmap, blockIdx.z), b = blockIdx.y, y0 = blockIdx.x * a.R;
     const int H = a.H, W = a.W, Cin = a.Cin;
     const int rows_out = min(a.R, H - y0);
     const int Wp = W + KS - 1;
@@ -505,7 +516,7 @@ __global__ __launch_bounds__(256) void dn_conv_kernel(ConvArgs a) {
 // ============================================================================
 template <int NT, int CB, bool POOL>
 __global__ __launch_bounds__(256) void dn_conv1x1_kernel(ConvArgs a) {
-    const int m = blockIdx.z, b = blockIdx.y;
+    const int m = member_of(a.mmap, blockIdx.z), b = blockIdx.y;
     const int H = a.H, W = a.W, Cin = a.Cin;
     const int lane = threadIdx.x & 63;
     const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -650,7 +661,7 @@ __global__ __launch_bounds__(kWgWaves * 64) void dn_wgrad3_kernel(WgArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int KS = 3, P = 1;
     constexpr int NTH = kWgWaves * 64;
-    const int m = blockIdx.z, grp = blockIdx.y, mg = blockIdx.x;
+    const int m = member_of(a.mmap, blockIdx.z), grp = blockIdx.y, mg = blockIdx.x;
     const int H = a.H, W = a.W, Cin = a.Cin, N = a.N;
     const int Kw = KS * KS * Cin;
     const int Wp = W + KS - 1;
@@ -848,7 +859,7 @@ template <int MT, int NT>
 __global__ __launch_bounds__(kWgWaves * 64) void dn_wgrad1_kernel(WgArgs a) {
     __shared__ __attribute__((aligned(16))) float red[kWgWaves - 1][MT * NT * 4 * 64];
     __shared__ float bnl[2 * kWg1MaxH];
-    const int m = blockIdx.z, grp = blockIdx.y;
+    const int m = member_of(a.mmap, blockIdx.z), grp = blockIdx.y;
     const int Cin = a.Cin, N = a.N;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -964,8 +975,9 @@ __global__ __launch_bounds__(kWgWaves * 64) void dn_wgrad1_kernel(WgArgs a) {
 
 // grads[w_off + e] = sum_g part[g][e]  (fixed order: deterministic)
 __global__ void dn_wgrad_reduce_kernel(const float* __restrict__ part, long long part_ms, int G, long long cnt,
-                                       float* __restrict__ grads, long long g_ms, long long w_off) {
-    const int m = blockIdx.y;
+                                       float* __restrict__ grads, long long g_ms, long long w_off,
+                                       const int* __restrict__ mmap) {
+    const int m = member_of(mmap, blockIdx.y);
     const float* pm = part + m * part_ms;
     for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < cnt; e += (long long)gridDim.x * blockDim.x) {
         float s = 0.f;
@@ -977,8 +989,9 @@ __global__ void dn_wgrad_reduce_kernel(const float* __restrict__ part, long long
 // Padded weight copies.  Forward: dst[(tap*cin4 + c)][n] = w[tap][c][n].
 // Input gradient (transpose = 1): dst[(tap'*cout4 + f)][c] = w[KS^2-1-tap'][c][f].
 __global__ void dn_prep_kernel(const float* __restrict__ params, long long p_ms, long long w_off, float* __restrict__ dst,
-                               long long d_ms, int taps, int cin, int cout, int rows, int n16, int transpose) {
-    const int m = blockIdx.y;
+                               long long d_ms, int taps, int cin, int cout, int rows, int n16, int transpose,
+                               const int* __restrict__ mmap) {
+    const int m = member_of(mmap, blockIdx.y);
     const float* w = params + m * p_ms + w_off;
     float* d = dst + m * d_ms;
     const int total = rows * n16;
@@ -1027,7 +1040,7 @@ __device__ __forceinline__ void stv(float* p, const float (&v)[V]) {
 template <int V>
 __global__ __launch_bounds__(256) void dn_bn_stats_kernel(BnArgs a, double* __restrict__ part, int S, int bs) {
     __shared__ double red[4];
-    const int h = blockIdx.x, sl = blockIdx.y, m = blockIdx.z, tid = threadIdx.x;
+    const int h = blockIdx.x, sl = blockIdx.y, m = member_of(a.mmap, blockIdx.z), tid = threadIdx.x;
     const int H = a.H, W = a.W, Cv = (a.Cin - a.c0) / V;
     const int rowv = W * Cv;
     const long long bstride = (long long)H * W * a.x_ps;
@@ -1060,7 +1073,7 @@ __global__ __launch_bounds__(256) void dn_bn_stats_kernel(BnArgs a, double* __re
 
 // The head site: z = ELU(x scale + shift) stored for the GAP (dn_bn_coef ran first)
 __global__ __launch_bounds__(256) void dn_bn_apply_kernel(BnArgs a) {
-    const int row = blockIdx.x, m = blockIdx.y, tid = threadIdx.x;
+    const int row = blockIdx.x, m = member_of(a.mmap, blockIdx.y), tid = threadIdx.x;
     const int H = a.H, W = a.W, Cin = a.Cin;
     const int b = row / H, h = row - b * H;
     const int rowe = W * Cin;
@@ -1081,7 +1094,7 @@ __global__ __launch_bounds__(256) void dn_bn_apply_kernel(BnArgs a) {
 // as this site's totals, then the moving averages; evaluation: the moving
 // averages.  Writes (mean, inv, scale = gamma inv, shift = beta - mean scale).
 __global__ __launch_bounds__(64) void dn_bn_coef_kernel(BnArgs a, const double* __restrict__ part, int S) {
-    const int m = blockIdx.x;
+    const int m = member_of(a.mmap, blockIdx.x);
     const int H = a.H, rowe = a.W * a.Cin;
     for (int h = threadIdx.x; h < H; h += 64) {
         float mean, var;
@@ -1146,7 +1159,7 @@ __device__ __forceinline__ void bn_dy(const BnArgs& a, const float (&x)[V], floa
 template <int V>
 __global__ __launch_bounds__(256) void dn_bn_bwd_reduce_kernel(BnArgs a, double* __restrict__ part, int S, int bs) {
     __shared__ double red[4];
-    const int h = blockIdx.x, sl = blockIdx.y, m = blockIdx.z, tid = threadIdx.x;
+    const int h = blockIdx.x, sl = blockIdx.y, m = member_of(a.mmap, blockIdx.z), tid = threadIdx.x;
     const int H = a.H, W = a.W, Cin = a.Cin, Cv = Cin / V;
     const int rowe = W * Cin, rowv = W * Cv;
     const float* coef = a.coef + m * a.coef_ms;
@@ -1184,7 +1197,7 @@ __global__ __launch_bounds__(256) void dn_bn_bwd_reduce_kernel(BnArgs a, double*
 // grid (member), one thread per image row h: the S slice partials summed in fixed
 // order into slot 0 (each thread reads and writes only its own h), dgamma / dbeta
 __global__ __launch_bounds__(64) void dn_bn_bwd_fold_kernel(BnArgs a, double* __restrict__ part, int S) {
-    const int m = blockIdx.x, H = a.H;
+    const int m = member_of(a.mmap, blockIdx.x), H = a.H;
     for (int h = threadIdx.x; h < H; h += 64) {
         double sdy = 0.0, sdyx = 0.0;
         for (int sl = 0; sl < S; ++sl) {
@@ -1205,7 +1218,7 @@ __global__ __launch_bounds__(64) void dn_bn_bwd_fold_kernel(BnArgs a, double* __
 // many slices (sample x row segment): lane l sums slices l, l + 64, ... in order, then a
 // fixed butterfly; slot 0 and the gradients as dn_bn_bwd_fold
 __global__ __launch_bounds__(64) void dn_bn_bwd_fold_wide_kernel(BnArgs a, double* __restrict__ part, int S) {
-    const int h = blockIdx.x, m = blockIdx.y, H = a.H, lane = threadIdx.x;
+    const int h = blockIdx.x, m = member_of(a.mmap, blockIdx.y), H = a.H, lane = threadIdx.x;
     double sdy = 0.0, sdyx = 0.0;
     for (int sl = lane; sl < S; sl += 64) {
         const double* o = part + (((long long)m * S + sl) * H + h) * 2;
@@ -1230,7 +1243,7 @@ __global__ __launch_bounds__(64) void dn_bn_bwd_fold_wide_kernel(BnArgs a, doubl
 
 template <int V>
 __global__ __launch_bounds__(256) void dn_bn_bwd_apply_kernel(BnArgs a, const double* __restrict__ part, int S) {
-    const int tid = threadIdx.x & 127, m = blockIdx.y;
+    const int tid = threadIdx.x & 127, m = member_of(a.mmap, blockIdx.y);
     const int row = blockIdx.x * 2 + (threadIdx.x >> 7);
     const int H = a.H, W = a.W, Cin = a.Cin, Cv = Cin / V;
     if (row >= a.B * H) return;
@@ -1274,8 +1287,8 @@ __global__ __launch_bounds__(256) void dn_bn_bwd_apply_kernel(BnArgs a, const do
 template <int V>
 __global__ __launch_bounds__(256) void dn_pool_fwd_kernel(const float* __restrict__ t, long long t_ms,
                                                           float* __restrict__ out, long long o_ms, int o_ps, int B,
-                                                          int H, int W, int C) {
-    const int m = blockIdx.y, H2 = H / 2, W2 = W / 2, Cv = C / V;
+                                                          int H, int W, int C, const int* __restrict__ mmap) {
+    const int m = member_of(mmap, blockIdx.y), H2 = H / 2, W2 = W / 2, Cv = C / V;
     const int row = blockIdx.x * 2 + (threadIdx.x >> 7), tid = threadIdx.x & 127;
     if (row >= B * H2) return;
     const int b = row / H2, y = row - b * H2;
@@ -1300,8 +1313,8 @@ __global__ __launch_bounds__(256) void dn_pool_fwd_kernel(const float* __restric
 template <int V>
 __global__ __launch_bounds__(256) void dn_pool_bwd_kernel(const float* __restrict__ dcat, long long d_ms, int d_ps,
                                                           float* __restrict__ dt, long long t_ms, int B, int H, int W,
-                                                          int C) {
-    const int m = blockIdx.y, H2 = H / 2, W2 = W / 2, Cv = C / V;
+                                                          int C, const int* __restrict__ mmap) {
+    const int m = member_of(mmap, blockIdx.y), H2 = H / 2, W2 = W / 2, Cv = C / V;
     const int row = blockIdx.x * 2 + (threadIdx.x >> 7), tid = threadIdx.x & 127;
     if (row >= B * H) return;
     const int b = row / H, y = row - b * H;
@@ -1337,11 +1350,12 @@ struct HeadArgs {
     const int* labels; const int* order; long long ord_ms; long long row0;
     float* loss_out; float* loss_sum; int* correct;
     int B, HW, C, classes, train;
+    const int* mmap;   // active member table (member_of)
 };
 
 __global__ __launch_bounds__(256) void dn_head_fwd_kernel(HeadArgs a) {
     extern __shared__ __attribute__((aligned(16))) float hs[];
-    const int b = blockIdx.x, m = blockIdx.y, tid = threadIdx.x;
+    const int b = blockIdx.x, m = member_of(a.mmap, blockIdx.y), tid = threadIdx.x;
     const int C = a.C, K = a.classes, HW = a.HW, B = a.B;
     float* g = hs;          // [C]
     float* lg = hs + C;     // [K]
@@ -1388,7 +1402,7 @@ __global__ __launch_bounds__(256) void dn_head_fwd_kernel(HeadArgs a) {
 // dg = dlogits . wd^T.  Eval: loss_sum += sum CE, correct += sum correct.
 __global__ __launch_bounds__(256) void dn_head_reduce_kernel(HeadArgs a, long long n_params) {
     __shared__ double red[4];
-    const int m = blockIdx.x, tid = threadIdx.x;
+    const int m = member_of(a.mmap, blockIdx.x), tid = threadIdx.x;
     const int C = a.C, K = a.classes, B = a.B;
     const float* hm = a.ce + m * a.h_ms;
     double s = 0.0, cor = 0.0;
@@ -1444,8 +1458,9 @@ __global__ __launch_bounds__(256) void dn_penalty_kernel(const float* __restrict
 // Keras Adam with the l2(1e-4) gradient 2e-4 w folded in (every DenseNet tensor is
 // regularised: conv kernels, gamma/beta, dense kernel + bias -- densenet.py:24-33, 188-191).
 __global__ void dn_adam_kernel(float* __restrict__ params, float* __restrict__ grads, float* __restrict__ mo,
-                               float* __restrict__ vo, long long p_ms, long long n, const float* __restrict__ lr, int t) {
-    const int m = blockIdx.y;
+                               float* __restrict__ vo, long long p_ms, long long n, const float* __restrict__ lr, int t,
+                               const int* __restrict__ mmap) {
+    const int m = member_of(mmap, blockIdx.y);
     const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
     const double corr = sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t));
     const float lr_t = (float)(lr[m] * corr);
@@ -1465,6 +1480,29 @@ __global__ void dn_adam_kernel(float* __restrict__ params, float* __restrict__ g
 // Host plan
 // ============================================================================
 enum Kind { K_CONV0 = 0, K_DENSE = 1, K_TRANS = 2, K_HEAD = 3 };
+
+// mpo_dn_step_work walks the enqueue functions of a train step with a tally set on its
+// thread: every launch adds its grid to the tally instead of running, so the figures
+// cannot drift from what a step launches.  No HIP call is made while a tally is set.
+struct Tally {
+    long long workgroups = 0, launches = 0;
+};
+thread_local Tally* g_tally = nullptr;
+
+#define DN_LAUNCH(kern, grid, block, lds, stream, ...)                           \
+    do {                                                                         \
+        if (g_tally) {                                                           \
+            const dim3 g_ = (grid);                                              \
+            g_tally->workgroups += (long long)g_.x * g_.y * g_.z;                \
+            ++g_tally->launches;                                                 \
+        } else {                                                                 \
+            hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);     \
+        }                                                                        \
+    } while (0)
+#define DN_LAUNCH_CHECK()                \
+    do {                                 \
+        if (!g_tally) MPO_LAUNCH_CHECK(); \
+    } while (0)
 
 struct Layer {
     int kind, stage, H, W, cin, cout, ks, coff;
@@ -1490,6 +1528,12 @@ struct DnPlan {
     long long dz_off = 0, dz_ms = 0, dt_off = 0, dt_ms = 0, part_off = 0, part_ms = 0, part2_off = 0, part2_ms = 0;
     long long part3_off = 0, part3_ms = 0;
     long long head_off = 0, head_ms = 0, lr_off = 0;
+    // mpo_dn_set_active: the active members' indices, ascending (host copy of the device
+    // table at map_off, beside the lr table); every grid spans na members
+    long long map_off = 0;
+    std::vector<int> act_list;
+    int na = 0;
+    const int* mmap() const { return reinterpret_cast<const int*>(act + map_off); }
     long long bnp_off = 0;
     long long bnt_off = 0;      // fp64 BN totals of the latest site [n][H][2]      // fp64 BN slice partials [n][S][H][2] (shared by all sites)
     std::vector<int> bn_S, bn_bs;   // per layer: batch slices and samples per slice
@@ -1699,22 +1743,29 @@ int build_plan(DnPlan& p) {
     p.head_off = ar.take((long long)B * hd.cin * 2 + (long long)B * hd.cout + 2LL * B, &p.head_ms);
     p.lr_off = ar.used;   // per-member learning rates
     ar.used += (p.n + 63) & ~63LL;
+    p.map_off = ar.used;  // active member table (int32 [n])
+    ar.used += (p.n + 63) & ~63LL;
     p.act_floats = ar.used;
+    p.act_list.resize(p.n);
+    for (int i = 0; i < p.n; ++i) p.act_list[i] = i;
+    p.na = p.n;
     return MPO_OK;
 }
 
 template <int KS, int NT>
 void launch_conv_t(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
     auto kern = dn_conv_kernel<KS, NT>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a);
+    if (!g_tally)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    DN_LAUNCH(kern, grid, dim3(256), lds, s, a);
 }
 
 template <int NT>
 void launch_wg3_t(const WgArgs& a, dim3 grid, size_t lds, hipStream_t s) {
     auto kern = dn_wgrad3_kernel<NT>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, grid, dim3(kWgWaves * 64), lds, s, a);
+    if (!g_tally)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    DN_LAUNCH(kern, grid, dim3(kWgWaves * 64), lds, s, a);
 }
 
 // dn_conv1x1_kernel: a 2 x 8 patch per wave (even H, W % 8 == 0), float4 channel
@@ -1727,8 +1778,8 @@ bool conv1x1_ok(const ConvArgs& a) {
 
 template <int NT, int CB>
 void launch_c1x1(const ConvArgs& a, dim3 grid, hipStream_t s) {
-    if (a.pool) hipLaunchKernelGGL((dn_conv1x1_kernel<NT, CB, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((dn_conv1x1_kernel<NT, CB, false>), grid, dim3(256), 0, s, a);
+    if (a.pool) DN_LAUNCH((dn_conv1x1_kernel<NT, CB, true>), grid, dim3(256), 0, s, a);
+    else DN_LAUNCH((dn_conv1x1_kernel<NT, CB, false>), grid, dim3(256), 0, s, a);
 }
 
 template <int NT>
@@ -1751,7 +1802,7 @@ int launch_conv1x1(const ConvArgs& a, int n_members, int B, hipStream_t s) {
         case 3: launch_c1x1_cb<3>(a, grid, cb, s); break;
         default: launch_c1x1_cb<4>(a, grid, cb, s); break;
     }
-    MPO_LAUNCH_CHECK();
+    DN_LAUNCH_CHECK();
     return MPO_OK;
 }
 
@@ -1779,10 +1830,10 @@ int launch_conv(const ConvArgs& a, int n_members, int B, hipStream_t s) {
 template <int MT>
 void launch_wg1_mt(const WgArgs& a, dim3 grid, int nt, hipStream_t s) {
     switch (nt) {
-        case 1: hipLaunchKernelGGL((dn_wgrad1_kernel<MT, 1>), grid, dim3(kWgWaves * 64), 0, s, a); break;
-        case 2: hipLaunchKernelGGL((dn_wgrad1_kernel<MT, 2>), grid, dim3(kWgWaves * 64), 0, s, a); break;
-        case 3: hipLaunchKernelGGL((dn_wgrad1_kernel<MT, 3>), grid, dim3(kWgWaves * 64), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((dn_wgrad1_kernel<MT, 4>), grid, dim3(kWgWaves * 64), 0, s, a); break;
+        case 1: DN_LAUNCH((dn_wgrad1_kernel<MT, 1>), grid, dim3(kWgWaves * 64), 0, s, a); break;
+        case 2: DN_LAUNCH((dn_wgrad1_kernel<MT, 2>), grid, dim3(kWgWaves * 64), 0, s, a); break;
+        case 3: DN_LAUNCH((dn_wgrad1_kernel<MT, 3>), grid, dim3(kWgWaves * 64), 0, s, a); break;
+        case 4: DN_LAUNCH((dn_wgrad1_kernel<MT, 4>), grid, dim3(kWgWaves * 64), 0, s, a); break;
         default: break;
     }
 }
@@ -1834,16 +1885,16 @@ int enqueue_prep(DnPlan& p, bool with_dgrad, hipStream_t s) {
         if (ly.kind == K_HEAD) continue;
         const int taps = ly.ks * ly.ks;
         const long long wms = (long long)ly.wf_rows * ly.wf_n16;
-        hipLaunchKernelGGL(dn_prep_kernel, flat_grid(wms, p.n), dim3(256), 0, s, p.params, p.n_params, ly.w_off,
-                           p.act + ly.wf_off, ((wms + 63) & ~63LL), taps, ly.cin, ly.cout, ly.wf_rows, ly.wf_n16, 0);
+        DN_LAUNCH(dn_prep_kernel, flat_grid(wms, p.na), dim3(256), 0, s, p.params, p.n_params, ly.w_off,
+                  p.act + ly.wf_off, ((wms + 63) & ~63LL), taps, ly.cin, ly.cout, ly.wf_rows, ly.wf_n16, 0, p.mmap());
         if (with_dgrad && ly.kind != K_CONV0) {
             const long long dms = (long long)ly.wd_rows * ly.wd_n16;
-            hipLaunchKernelGGL(dn_prep_kernel, flat_grid(dms, p.n), dim3(256), 0, s, p.params, p.n_params, ly.w_off,
-                               p.act + ly.wd_off_act, ((dms + 63) & ~63LL), taps, ly.cin, ly.cout, ly.wd_rows,
-                               ly.wd_n16, 1);
+            DN_LAUNCH(dn_prep_kernel, flat_grid(dms, p.na), dim3(256), 0, s, p.params, p.n_params, ly.w_off,
+                      p.act + ly.wd_off_act, ((dms + 63) & ~63LL), taps, ly.cin, ly.cout, ly.wd_rows,
+                      ly.wd_n16, 1, p.mmap());
         }
     }
-    MPO_LAUNCH_CHECK();
+    DN_LAUNCH_CHECK();
     return MPO_OK;
 }
 
@@ -1865,6 +1916,7 @@ bool pool_vec4(int C, int ps, long long ms_a, long long ms_b, const float* pa, c
 
 BnArgs bn_args(DnPlan& p, const Layer& ly, bool train) {
     BnArgs a{};
+    a.mmap = p.mmap();
     const int s = ly.stage;
     a.x = p.act + p.cat_off[s]; a.x_ms = p.cat_ms[s]; a.x_ps = p.sC[s];
     a.z = ly.z_off >= 0 ? p.act + ly.z_off : nullptr;
@@ -1881,6 +1933,7 @@ BnArgs bn_args(DnPlan& p, const Layer& ly, bool train) {
 HeadArgs head_args(DnPlan& p, const int* labels, const int* order, long long ord_ms, long long row0, bool train) {
     const Layer& hd = p.layers.back();
     HeadArgs h{};
+    h.mmap = p.mmap();
     h.z = p.act + hd.z_off; h.z_ms = ((long long)p.B * hd.H * hd.W * hd.cin + 63) & ~63LL;
     h.params = p.params; h.p_ms = p.n_params; h.wd_off = p.wd_off; h.bd_off = p.bd_off;
     h.grads = p.grads;
@@ -1894,11 +1947,12 @@ HeadArgs head_args(DnPlan& p, const int* labels, const int* order, long long ord
 
 int enqueue_forward(DnPlan& p, const float* x, const int* labels, const int* order, long long ord_ms, long long row0,
                     bool train, float* loss_out, float* loss_sum, int* correct, hipStream_t s) {
-    const int B = p.B, n = p.n;
+    const int B = p.B, n = p.na;   // grids span the active members
     for (auto& ly : p.layers) {
         const int st = ly.stage;
         if (ly.kind == K_CONV0) {
             ConvArgs c{};
+            c.mmap = p.mmap();
             c.in = x; c.in_ps = ly.cin; c.order = order; c.ord_ms = ord_ms; c.row0 = row0;
             c.img_floats = (long long)ly.H * ly.W * ly.cin;
             c.w = p.act + ly.wf_off; c.w_ms = ((long long)ly.wf_rows * ly.wf_n16 + 63) & ~63LL;
@@ -1920,20 +1974,21 @@ int enqueue_forward(DnPlan& p, const float* x, const int* labels, const int* ord
         }
         if (train) {
             auto kern = bn_vec4(bn) ? dn_bn_stats_kernel<4> : dn_bn_stats_kernel<1>;
-            hipLaunchKernelGGL(kern, dim3(ly.H, p.bn_S[li], n), dim3(256), 0, s, bn, bnp, p.bn_S[li], p.bn_bs[li]);
+            DN_LAUNCH(kern, dim3(ly.H, p.bn_S[li], n), dim3(256), 0, s, bn, bnp, p.bn_S[li], p.bn_bs[li]);
         }
-        hipLaunchKernelGGL(dn_bn_coef_kernel, dim3(n), dim3(64), 0, s, bn, (const double*)bnp, p.bn_S[li]);
+        DN_LAUNCH(dn_bn_coef_kernel, dim3(n), dim3(64), 0, s, bn, (const double*)bnp, p.bn_S[li]);
         if (ly.kind == K_HEAD)   // the head's GAP reads z: the only site that stores it
-            hipLaunchKernelGGL(dn_bn_apply_kernel, dim3(B * ly.H, n), dim3(256), 0, s, bn);
+            DN_LAUNCH(dn_bn_apply_kernel, dim3(B * ly.H, n), dim3(256), 0, s, bn);
         if (ly.kind == K_HEAD) {
             HeadArgs h = head_args(p, labels, order, ord_ms, row0, train);
             h.loss_out = loss_out; h.loss_sum = loss_sum; h.correct = correct;
             const size_t lds = (size_t)(h.C + h.classes) * sizeof(float);
-            hipLaunchKernelGGL(dn_head_fwd_kernel, dim3(B, n), dim3(256), lds, s, h);
-            hipLaunchKernelGGL(dn_head_reduce_kernel, dim3(n), dim3(256), 0, s, h, p.n_params);
+            DN_LAUNCH(dn_head_fwd_kernel, dim3(B, n), dim3(256), lds, s, h);
+            DN_LAUNCH(dn_head_reduce_kernel, dim3(n), dim3(256), 0, s, h, p.n_params);
             continue;
         }
         ConvArgs c{};
+        c.mmap = p.mmap();
         c.in = bn.x; c.in_ms = bn.x_ms; c.in_ps = bn.x_ps;   // cat: the conv stages ELU(BN(x))
         c.bnc = bn.coef; c.bnc_ms = bn.coef_ms;
         c.w = p.act + ly.wf_off; c.w_ms = ((long long)ly.wf_rows * ly.wf_n16 + 63) & ~63LL;
@@ -1955,12 +2010,12 @@ int enqueue_forward(DnPlan& p, const float* x, const int* labels, const int* ord
             DN_TRY(launch_conv<1>(c, n, B, s));
             const bool v4 = pool_vec4(ly.cout, p.sC[st + 1], tms, p.cat_ms[st + 1], p.act + ly.t_off,
                                       p.act + p.cat_off[st + 1]);
-            hipLaunchKernelGGL(v4 ? dn_pool_fwd_kernel<4> : dn_pool_fwd_kernel<1>,
-                               dim3((B * (ly.H / 2) + 1) / 2, n), dim3(256), 0, s, p.act + ly.t_off, tms,
-                               p.act + p.cat_off[st + 1], p.cat_ms[st + 1], p.sC[st + 1], B, ly.H, ly.W, ly.cout);
+            DN_LAUNCH(v4 ? dn_pool_fwd_kernel<4> : dn_pool_fwd_kernel<1>,
+                      dim3((B * (ly.H / 2) + 1) / 2, n), dim3(256), 0, s, p.act + ly.t_off, tms,
+                      p.act + p.cat_off[st + 1], p.cat_ms[st + 1], p.sC[st + 1], B, ly.H, ly.W, ly.cout, p.mmap());
         }
     }
-    MPO_LAUNCH_CHECK();
+    DN_LAUNCH_CHECK();
     return MPO_OK;
 }
 
@@ -1969,16 +2024,16 @@ void enqueue_bn_bwd(DnPlan& p, const BnArgs& bn, int li, hipStream_t s, int fuse
     const int S = fused_S > 0 ? fused_S : p.bn_S[li];
     const bool v4 = bn_vec4(bn);
     if (fused_S <= 0)   // else the input-gradient conv's epilogue wrote the slice partials
-        hipLaunchKernelGGL(v4 ? dn_bn_bwd_reduce_kernel<4> : dn_bn_bwd_reduce_kernel<1>, dim3(bn.H, S, p.n),
-                           dim3(256), 0, s, bn, bnp, S, p.bn_bs[li]);
-    if (fused_S > 0) hipLaunchKernelGGL(dn_bn_bwd_fold_wide_kernel, dim3(bn.H, p.n), dim3(64), 0, s, bn, bnp, S);
-    else hipLaunchKernelGGL(dn_bn_bwd_fold_kernel, dim3(p.n), dim3(64), 0, s, bn, bnp, S);
-    hipLaunchKernelGGL(v4 ? dn_bn_bwd_apply_kernel<4> : dn_bn_bwd_apply_kernel<1>, dim3((p.B * bn.H + 1) / 2, p.n),
-                       dim3(256), 0, s, bn, (const double*)bnp, S);
+        DN_LAUNCH(v4 ? dn_bn_bwd_reduce_kernel<4> : dn_bn_bwd_reduce_kernel<1>, dim3(bn.H, S, p.na),
+                  dim3(256), 0, s, bn, bnp, S, p.bn_bs[li]);
+    if (fused_S > 0) DN_LAUNCH(dn_bn_bwd_fold_wide_kernel, dim3(bn.H, p.na), dim3(64), 0, s, bn, bnp, S);
+    else DN_LAUNCH(dn_bn_bwd_fold_kernel, dim3(p.na), dim3(64), 0, s, bn, bnp, S);
+    DN_LAUNCH(v4 ? dn_bn_bwd_apply_kernel<4> : dn_bn_bwd_apply_kernel<1>, dim3((p.B * bn.H + 1) / 2, p.na),
+              dim3(256), 0, s, bn, (const double*)bnp, S);
 }
 
 int enqueue_backward(DnPlan& p, const float* x, const int* order, long long ord_ms, long long row0, hipStream_t s) {
-    const int B = p.B, n = p.n;
+    const int B = p.B, n = p.na;   // grids span the active members
     // Weight gradients on a side stream s2, each forked after its dOut is final on s.
     // Disjoint from what s writes meanwhile: a dense layer's dOut is its growth slice
     // [coff, coff + g) of dcat, and the BN backward of it and of every earlier layer
@@ -1986,7 +2041,7 @@ int enqueue_backward(DnPlan& p, const float* x, const int* order, long long ord_
     // backward); the slabs and the gradient slots are s2's alone.  The transition dOut
     // buffer dt is shared by the transitions, so s waits for s2 before each pool
     // backward refills it; s waits for everything at the end (Adam reads the gradients).
-    hipStream_t s2 = p.side.get(s);
+    hipStream_t s2 = g_tally ? nullptr : p.side.get(s);   // a tally never touches HIP
     p.side2.slot = 1;
     hipStream_t s3 = s2 && p.wg2 ? p.side2.get(s) : nullptr;
     p.side3.slot = 2;
@@ -2005,6 +2060,7 @@ int enqueue_backward(DnPlan& p, const float* x, const int* order, long long ord_
         }
         // dOut of this layer's conv and the input it saw
         WgArgs w{};
+        w.mmap = p.mmap();
         w.H = ly.H; w.W = ly.W; w.Cin = ly.cin; w.N = ly.cout; w.R = ly.Rw; w.spg = ly.spg; w.B = B; w.kw = ly.kw;
         const int nws = s4 ? 3 : (s3 ? 2 : 1), ws_i = wgi % nws;
         ++wgi;
@@ -2020,9 +2076,9 @@ int enqueue_backward(DnPlan& p, const float* x, const int* order, long long ord_
             if (s4) MPO_HIP(p.side3.join(s, s4));
             const bool v4 = pool_vec4(ly.cout, p.sC[st + 1], p.dt_ms, p.cat_ms[st + 1], p.act + p.dt_off,
                                       p.act + p.dcat_off[st + 1]);
-            hipLaunchKernelGGL(v4 ? dn_pool_bwd_kernel<4> : dn_pool_bwd_kernel<1>, dim3((B * ly.H + 1) / 2, n),
-                               dim3(256), 0, s, p.act + p.dcat_off[st + 1],
-                               p.cat_ms[st + 1], p.sC[st + 1], p.act + p.dt_off, p.dt_ms, B, ly.H, ly.W, ly.cout);
+            DN_LAUNCH(v4 ? dn_pool_bwd_kernel<4> : dn_pool_bwd_kernel<1>, dim3((B * ly.H + 1) / 2, n),
+                      dim3(256), 0, s, p.act + p.dcat_off[st + 1],
+                      p.cat_ms[st + 1], p.sC[st + 1], p.act + p.dt_off, p.dt_ms, B, ly.H, ly.W, ly.cout, p.mmap());
             dout = p.act + p.dt_off; dout_ms = p.dt_ms; dout_ps = ly.cout;
         } else {
             dout = p.act + p.dcat_off[st] + ly.coff; dout_ms = p.cat_ms[st]; dout_ps = p.sC[st];
@@ -2049,12 +2105,13 @@ int enqueue_backward(DnPlan& p, const float* x, const int* order, long long ord_
         }
         DN_TRY(launch_wgrad(w, ly.ks, n, ly.G, sw));
         const long long cnt = (long long)ly.ks * ly.ks * ly.cin * ly.cout;
-        hipLaunchKernelGGL(dn_wgrad_reduce_kernel, flat_grid(cnt, n), dim3(256), 0, sw, (const float*)w.part,
-                           w.part_ms, ly.G, cnt, p.grads, p.n_params, ly.w_off);
+        DN_LAUNCH(dn_wgrad_reduce_kernel, flat_grid(cnt, n), dim3(256), 0, sw, (const float*)w.part,
+                  w.part_ms, ly.G, cnt, p.grads, p.n_params, ly.w_off, p.mmap());
         if (ly.kind == K_CONV0) continue;
         // input gradient: 'same' conv of dOut with the rotated, transposed kernel -> dz
         BnArgs bn = bn_args(p, ly, true);
         ConvArgs c{};
+        c.mmap = p.mmap();
         c.in = dout; c.in_ms = dout_ms; c.in_ps = dout_ps;
         c.w = p.act + ly.wd_off_act; c.w_ms = ((long long)ly.wd_rows * ly.wd_n16 + 63) & ~63LL;
         c.out = p.act + p.dz_off; c.out_ms = p.dz_ms; c.out_ps = ly.cin;
@@ -2076,7 +2133,20 @@ int enqueue_backward(DnPlan& p, const float* x, const int* order, long long ord_
     if (s2) MPO_HIP(p.side.join(s, s2));
     if (s3) MPO_HIP(p.side2.join(s, s3));
     if (s4) MPO_HIP(p.side3.join(s, s4));
-    MPO_LAUNCH_CHECK();
+    DN_LAUNCH_CHECK();
+    return MPO_OK;
+}
+
+// One train step of the active members (mpo_dn_train_step; tallied by mpo_dn_step_work).
+int enqueue_train(DnPlan& p, const float* x, const int* labels, const int* order, long long ord_ms, long long row0,
+                  int step, float* loss_out, hipStream_t s) {
+    if (p.na == 0) return MPO_OK;   // every member retired: nothing to launch
+    DN_TRY(enqueue_prep(p, true, s));
+    DN_TRY(enqueue_forward(p, x, labels, order, ord_ms, row0, true, loss_out, nullptr, nullptr, s));
+    DN_TRY(enqueue_backward(p, x, order, ord_ms, row0, s));
+    DN_LAUNCH(dn_adam_kernel, flat_grid(p.n_params, p.na), dim3(256), 0, s, p.params, p.grads, p.m, p.v, p.n_params,
+              p.n_params, (const float*)(p.act + p.lr_off), step + 1, p.mmap());
+    DN_LAUNCH_CHECK();
     return MPO_OK;
 }
 
@@ -2165,6 +2235,9 @@ int mpo_dn_bind(void* handle, float* params, float* grads, float* adam_m, float*
     p.params = params; p.grads = grads; p.m = adam_m; p.v = adam_v; p.state = state; p.act = act;
     MPO_HIP(hipMemcpyAsync(act + p.lr_off, lr, sizeof(float) * p.n, hipMemcpyHostToDevice,
                            static_cast<hipStream_t>(stream)));
+    if (p.na > 0)   // the active member table (a mask may have been set before bind)
+        MPO_HIP(hipMemcpyAsync(act + p.map_off, p.act_list.data(), sizeof(int) * p.na, hipMemcpyHostToDevice,
+                               static_cast<hipStream_t>(stream)));
     MPO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     p.bound = true;
     return MPO_OK;
@@ -2178,13 +2251,49 @@ int mpo_dn_train_step(void* handle, const float* x, const int32_t* labels, const
     DnPlan& p = *static_cast<DnPlan*>(handle);
     MPO_CHECK_ARG(p.bound, "mpo_dn_train_step: plan not bound");
     MPO_CHECK_ARG(step >= 0 && row0 >= 0 && row0 + p.B <= order_stride, "mpo_dn_train_step: batch outside the order table");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    DN_TRY(enqueue_prep(p, true, s));
-    DN_TRY(enqueue_forward(p, x, labels, order, order_stride, row0, true, loss_out, nullptr, nullptr, s));
-    DN_TRY(enqueue_backward(p, x, order, order_stride, row0, s));
-    hipLaunchKernelGGL(dn_adam_kernel, flat_grid(p.n_params, p.n), dim3(256), 0, s, p.params, p.grads, p.m, p.v,
-                       p.n_params, p.n_params, (const float*)(p.act + p.lr_off), (int)step + 1);
-    MPO_LAUNCH_CHECK();
+    return enqueue_train(p, x, labels, order, order_stride, row0, (int)step, loss_out, static_cast<hipStream_t>(stream));
+    MPO_GUARD_END
+}
+
+int mpo_dn_set_active(void* handle, const uint8_t* active, void* stream) {
+    MPO_GUARD_BEGIN
+    MPO_CHECK_ARG(handle && active, "mpo_dn_set_active: null pointer");
+    DnPlan& p = *static_cast<DnPlan*>(handle);
+    std::vector<int> list;
+    for (int i = 0; i < p.n; ++i)
+        if (active[i]) list.push_back(i);
+    if (list == p.act_list) return MPO_OK;
+    p.act_list.swap(list);
+    p.na = (int)p.act_list.size();
+    if (p.bound && p.na > 0) {
+        // stream order puts the copy after the steps enqueued so far (their side streams
+        // have joined `stream`); the wait keeps the host list ours to replace next time
+        hipStream_t s = static_cast<hipStream_t>(stream);
+        MPO_HIP(hipMemcpyAsync(p.act + p.map_off, p.act_list.data(), sizeof(int) * p.na, hipMemcpyHostToDevice, s));
+        MPO_HIP(hipStreamSynchronize(s));
+    }
+    return MPO_OK;
+    MPO_GUARD_END
+}
+
+int mpo_dn_step_work(const void* handle, int64_t* workgroups, int64_t* launches) {
+    MPO_GUARD_BEGIN
+    MPO_CHECK_ARG(handle && workgroups && launches, "mpo_dn_step_work: null pointer");
+    // the plan is only read: the tally makes every launch site count instead of launch.
+    // An unbound plan walks with stand-in arenas (offsets are added to them, nothing is
+    // dereferenced), so the kernel choices that look at alignment match a bound plan's.
+    DnPlan& p = *const_cast<DnPlan*>(static_cast<const DnPlan*>(handle));
+    alignas(256) static float stand_in[64];
+    float* const saved[6] = {p.params, p.grads, p.m, p.v, p.state, p.act};
+    if (!p.bound) p.params = p.grads = p.m = p.v = p.state = p.act = stand_in;
+    Tally t;
+    g_tally = &t;
+    const int rc = enqueue_train(p, stand_in, nullptr, reinterpret_cast<const int*>(stand_in), p.B, 0, 0, stand_in, nullptr);
+    g_tally = nullptr;
+    p.params = saved[0]; p.grads = saved[1]; p.m = saved[2]; p.v = saved[3]; p.state = saved[4]; p.act = saved[5];
+    if (rc != MPO_OK) return rc;
+    *workgroups = t.workgroups;
+    *launches = t.launches;
     return MPO_OK;
     MPO_GUARD_END
 }
@@ -2196,6 +2305,7 @@ int mpo_dn_eval_step(void* handle, const float* x, const int32_t* labels, const 
     DnPlan& p = *static_cast<DnPlan*>(handle);
     MPO_CHECK_ARG(p.bound, "mpo_dn_eval_step: plan not bound");
     MPO_CHECK_ARG(row0 >= 0 && row0 + p.B <= order_stride, "mpo_dn_eval_step: batch outside the order table");
+    if (p.na == 0) return MPO_OK;
     hipStream_t s = static_cast<hipStream_t>(stream);
     DN_TRY(enqueue_prep(p, false, s));
     DN_TRY(enqueue_forward(p, x, labels, order, order_stride, row0, false, nullptr, loss_sum, correct, s));
@@ -2208,8 +2318,8 @@ int mpo_dn_penalty(void* handle, float* out, void* stream) {
     MPO_CHECK_ARG(handle && out, "mpo_dn_penalty: null pointer");
     DnPlan& p = *static_cast<DnPlan*>(handle);
     MPO_CHECK_ARG(p.bound, "mpo_dn_penalty: plan not bound");
-    hipLaunchKernelGGL(dn_penalty_kernel, dim3(p.n), dim3(256), 0, static_cast<hipStream_t>(stream), p.params,
-                       p.n_params, p.n_params, out);
+    DN_LAUNCH(dn_penalty_kernel, dim3(p.n), dim3(256), 0, static_cast<hipStream_t>(stream), p.params,
+              p.n_params, p.n_params, out);
     MPO_LAUNCH_CHECK();
     return MPO_OK;
     MPO_GUARD_END

@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr
-from .population import kfold_split, train_folds  # noqa: F401 (kfold_split re-exported)
+from .population import _set_active, _step_work, kfold_split, train_folds  # noqa: F401 (kfold_split re-exported)
 
 KIND_NAMES = {0: "conv0", 1: "dense", 2: "trans", 3: "head"}
 
@@ -302,6 +302,18 @@ class DenseNetPopulation:
         for i, (p, s) in enumerate(init):
             self.set_params(i, p, s)
         self.step_count = 0
+        self.active = np.ones(self.n, dtype=bool)
+
+    # -- retiring members ---------------------------------------------------------
+    def set_active(self, mask):
+        """``mpo_dn_set_active``: as :meth:`PopulationEngine.set_active` -- retired
+        members cost no kernel work and keep their parameters, Adam and BN state and
+        ``loss`` / ``val_*`` entries (:meth:`penalty` still covers every member)."""
+        self.active = _set_active(self, lib().mpo_dn_set_active, mask)
+
+    def step_work(self):
+        """(workgroups, launches) of one train step under the current mask."""
+        return _step_work(self, lib().mpo_dn_step_work)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -373,12 +385,12 @@ class DenseNetPopulation:
 
     # -- full k-fold training -----------------------------------------------------
     def fit_folds(self, x, labels, folds, n_fold, epochs, record_train_loss=False, holdout=None, progress=None,
-                  stopping=None):
+                  stopping=None, retire_stopped=False):
         """Train every member for ``epochs`` on its fold (in order, no shuffle),
         validating once per epoch; val_loss = mean CE + l2 penalty (Keras).  The
-        loop is population.train_folds."""
+        loop is population.train_folds (``retire_stopped`` as there)."""
         return train_folds(self, x, labels, folds, n_fold, epochs, record_train_loss, holdout, progress, stopping,
-                           val_offset=self.penalty)
+                           val_offset=self.penalty, retire_stopped=retire_stopped)
 
 
 def synthetic_cifar(n=50000, img_dim=(32, 32, 3), classes=10, seed=0, device=None):

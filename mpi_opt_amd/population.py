@@ -219,6 +219,20 @@ class PopulationEngine:
         for i, p in enumerate(init):
             self.set_params(i, p)
         self.step_count = 0
+        self.active = np.ones(self.n, dtype=bool)
+
+    # -- retiring members ---------------------------------------------------------
+    def set_active(self, mask):
+        """``mpo_pop_set_active``: members with a false entry of ``mask`` [n] take no
+        part in the following train / eval steps (no kernel work; their parameters,
+        Adam state and ``loss`` / ``val_*`` entries are not written) until a later
+        mask brings them back.  An active member's bits do not change.  Waits for
+        the current stream; not capturable."""
+        self.active = _set_active(self, lib().mpo_pop_set_active, mask)
+
+    def step_work(self):
+        """(workgroups, launches) of one train step under the current mask."""
+        return _step_work(self, lib().mpo_pop_step_work)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -306,25 +320,51 @@ class PopulationEngine:
 
     # -- full k-fold training -----------------------------------------------------
     def fit_folds(self, x, labels, folds, n_fold, epochs, record_train_loss=False, holdout=None, progress=None,
-                  stopping=None):
+                  stopping=None, retire_stopped=False):
         """Train every member for ``epochs`` on its fold's training indices (in
         order, no shuffle), validating once per epoch (validate_every =
         count/batch, option3:260).  ``folds[i]`` is member i's fold index;
         ``progress(epoch, epochs)`` is called after each epoch's validation;
-        ``stopping`` (a :class:`~mpi_opt_amd.stopping.StopRule`) ends members early.
+        ``stopping`` (a :class:`~mpi_opt_amd.stopping.StopRule`) ends members early;
+        ``retire_stopped`` also takes them out of the steps the others still run
+        (:func:`train_folds`: their later entries are NaN).
         Returns {"val_loss": [n, epochs], "val_acc": [n, epochs], "epochs_run": [n], ...}."""
-        return train_folds(self, x, labels, folds, n_fold, epochs, record_train_loss, holdout, progress, stopping)
+        return train_folds(self, x, labels, folds, n_fold, epochs, record_train_loss, holdout, progress, stopping,
+                           retire_stopped=retire_stopped)
+
+
+def _set_active(eng, fn, mask):
+    """Shared by the two engines' ``set_active``: the mask as the C call's host bytes."""
+    m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0)
+    if m.size != eng.n:
+        raise ValueError(f"set_active: mask of {m.size} entries for {eng.n} members")
+    host = (ctypes.c_uint8 * eng.n)(*m.astype(np.uint8).tolist())
+    with torch.cuda.device(eng.device):
+        check(fn(eng._h, ctypes.cast(host, ctypes.c_void_p), _lib.stream_handle(eng.device)), fn.__name__)
+    return m.copy()
+
+
+def _step_work(eng, fn):
+    work, launches = ctypes.c_int64(), ctypes.c_int64()
+    check(fn(eng._h, ctypes.byref(work), ctypes.byref(launches)), fn.__name__)
+    return int(work.value), int(launches.value)
 
 
 def train_folds(eng, x, labels, folds, n_fold, epochs, record_train_loss=False, holdout=None, progress=None,
-                stopping=None, val_offset=None):
+                stopping=None, val_offset=None, retire_stopped=False):
     """The k-fold training loop shared by the MNIST and DenseNet populations
     (``eng.train_step`` / ``eval_reset`` / ``eval_step`` / ``val_loss_sum`` /
     ``val_correct``): members step in lock-step on full batches, every member on
     the first steps_per_epoch*B indices of its fold, validating on the first
     val_batches*B; what that leaves out (uneven folds, a partial last batch that
     Keras would still run) is reported in the history, never hidden.
-    ``val_offset()`` is added to the validation loss (DenseNet's l2 penalty)."""
+    ``val_offset()`` is added to the validation loss (DenseNet's l2 penalty).
+    ``retire_stopped`` (with a ``stopping`` rule and an engine that has
+    ``set_active``): members that stopped are retired from the engine after the
+    epoch's validation, so the epochs the others still run cost nothing for them;
+    every ``val_loss`` / ``val_acc`` entry past a member's stopping epoch is then
+    NaN (the member was not evaluated), everything up to it and ``epochs_run``
+    are unchanged, and the engine is left with every member active again."""
     n_samples = x.shape[0]
     B = eng.batch
     tr, va = [], []
@@ -345,6 +385,8 @@ def train_folds(eng, x, labels, folds, n_fold, epochs, record_train_loss=False, 
     val_loss = torch.zeros(eng.n, epochs, dtype=torch.float32, device=eng.device)
     val_acc = torch.zeros(eng.n, epochs, dtype=torch.float32, device=eng.device)
     state = stopping.start(eng.n) if stopping is not None else None
+    retire = bool(retire_stopped) and state is not None and hasattr(eng, "set_active")
+    retired = False
     tl = []
     for ep in range(epochs):
         for st in range(steps_per_epoch):
@@ -360,9 +402,18 @@ def train_folds(eng, x, labels, folds, n_fold, epochs, record_train_loss=False, 
         if progress is not None:
             progress(ep + 1, epochs)
         if state is not None:
-            state.update(ep, val_loss[:, ep].cpu().numpy(), val_acc[:, ep].cpu().numpy())
+            now = state.update(ep, val_loss[:, ep].cpu().numpy(), val_acc[:, ep].cpu().numpy())
             if state.all_stopped():
                 break
+            if retire and now.any():
+                eng.set_active(~state.stopped)
+                retired = True
+    if retired:
+        eng.set_active(np.ones(eng.n, dtype=bool))
+    if retire:
+        past = torch.from_numpy(np.arange(epochs)[None, :] >= state.epochs(epochs)[:, None]).to(eng.device)
+        val_loss[past] = float("nan")
+        val_acc[past] = float("nan")
     out = {"val_loss": val_loss.cpu().numpy(), "val_acc": val_acc.cpu().numpy(),
            "steps_per_epoch": steps_per_epoch, "val_batches": val_batches,
            "dropped_train_samples": dropped_tr, "dropped_val_samples": dropped_va,

@@ -20,7 +20,14 @@ validation pass (the reference validates every epoch, option3:260):
 
 A stopped member's history ends at its stopping epoch, so its figure of merit
 (the last validation loss, averaged over folds) is the one at that epoch; the
-population stops stepping once every member has stopped.
+population stops stepping once every member has stopped.  Until then a stopped
+member still steps with the others unless the fold loop retires it
+(``train_folds(..., retire_stopped=True)``, what ``TrialEvaluator`` asks for):
+after the epoch's ``StopState.update`` the loop hands ``~state.stopped`` to the
+engine's ``set_active`` (``mpo_pop_set_active`` / ``mpo_dn_set_active``), the
+retired members cost no kernel work in the epochs the others still run, and
+their raw ``val_loss`` / ``val_acc`` entries past the stopping epoch are NaN.
+Histories, ``epochs_run`` and figures of merit are the same either way.
 """
 from __future__ import annotations
 
