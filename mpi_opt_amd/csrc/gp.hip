@@ -589,8 +589,12 @@ __device__ __forceinline__ void score_finish_own_rows(double* kc, int wave, int 
     }
 
 // One workgroup = 4 waves looping over 16-candidate tiles (kBM) tile = blockIdx.x,
-// += gridDim.x (the grid is sized to the resident capacity); the next tile's
-// candidate rows are loaded while the current one is scored.
+// += gridDim.x (the grid is sized to the resident capacity).  Two workgroup
+// barriers per tile: B after phase 1 (K* complete) and D after phase 2.  The next
+// tile's candidate rows are staged into cs between them (cs is read only before B),
+// the rows of the tile after that load meanwhile, and the mu / q partials travel
+// through red without a barrier of their own (mu in two halves by tile parity; the
+// argument is at the two barriers).
 // FIN = 1 (every scoring launch): after its tile loop the workgroup finishes its own
 // candidates -- the (mu_n, q) rows it wrote (still largely in this XCD's L2) read
 // back 64 per wave with every lane live, the posterior and acquisitions as
@@ -609,7 +613,8 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
     const int np16 = a.np16;
     double* kc = smem;                          // [np16/4][64]: k-step ks at kc[ks*64]
     double* cs = kc + (size_t)np16 * BM;        // [BM][DP]
-    double* red = cs + BM * DP;                 // [S][BM] (mu) then [4][BM] (q)
+    double* red = cs + BM * DP;                 // mu partials [2][4][BM] (tile parity, share), then
+    double* redq = red + 2 * 4 * BM;            // q partials [4][BM] (wave); the last quarter of [S][BM] is unused
     int32_t* mls = reinterpret_cast<int32_t*>(red + S * BM);   // the 4 wave records of wmeta
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -632,7 +637,14 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
         const long long gm = (TILE) * BM + r;                                                  \
         raw[u] = (e < BM * DP && gm < a.m && c < a.d) ? __builtin_nontemporal_load(a.cand + gm * a.d + c) : 0.0; \
     }
+    // candidate tile / ls -> LDS
+#define MPO_STAGE_TILE                                                                         \
+    _Pragma("unroll") for (int u = 0; u < EPT; ++u)                                            \
+        if (tid + 256 * u < BM * DP) cs[tid + 256 * u] = raw[u] / ls_e[u];
+    // prologue: the first tile staged, the second one loading
     MPO_LOAD_TILE((long long)blockIdx.x)
+    MPO_STAGE_TILE
+    MPO_LOAD_TILE((long long)blockIdx.x + gridDim.x)
     __syncthreads();
     // the finishing wave (mu fold, phase 3, FIN's group finish): the wave whose phase-2
     // B stream (sw = (wave + blockIdx.x) & 3, below) carries the fewest groups
@@ -644,8 +656,12 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
         fw = __builtin_amdgcn_readfirstlane((lw - (int)blockIdx.x) & 3);
     }
 
-    // Phase-2 B-fragment stream of this wave (rotated by block so the heaviest one
-    // does not always land on the same SIMD).  B fragments arrive through asm loads
+    // Phase-2 B-fragment stream of this wave, rotated by block.  (The rotation was
+    // meant to keep the heaviest stream off one SIMD.  The workgroups resident on one
+    // CU are blockIdx.x apart by multiples of 256 and share blockIdx.x & 3, so it
+    // does not do that; the hardware's varying wave placement does,
+    // scripts/probes/wave_simd.hip.  It stays: the q fold's association follows it.)
+    // B fragments arrive through asm loads
     // with explicit vmcnt waits: the compiler's own waitcnt placement drained the
     // ring every iteration (vmcnt(0) before register copies).  The ring lives
     // inside phase 2 only and is drained at its end: a compiler copy of a ring
@@ -656,23 +672,31 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
     const int G = (a.dbg & 1) ? 0 : __builtin_amdgcn_readfirstlane(mw[1]);
     const double* bs = a.wfrag + (size_t)__builtin_amdgcn_readfirstlane(mw[0]) * 256 + lane;
 
+    // Phase-1 share of this wave: the observations are dealt to four shares (MFMA
+    // form: blocks of 16, t = share, += 4, so share 0 carries the extra block of
+    // T % 4 == 1; direct form: i-slots 4 share + (lane >> 4), += 16).  The share moves
+    // to the next wave every tile, so over four tiles every wave carries every share
+    // once.  With the shares pinned to the wave index, the two-barrier loop lost 4% at
+    // n = 600 (supposed cause: nothing re-aligns the waves between B and the next B
+    // any more, so where the wave with the extra block is also fw, its phase 3 and
+    // its longer phase 1 are on the critical path of every tile); with them moving
+    // it gains at every n measured.  A share's mu partial goes to the share's row of
+    // red whichever wave computed it: the fold below adds the rows in share order,
+    // and the bits do not depend on the rotation.
+    int vs = (wave + (int)blockIdx.x) & 3;
+    double* redm = red;   // this tile's mu rows; the other parity's: red + 4 * BM
+
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const long long m0 = tile * BM;
 
-    // ---- phase 0: candidate tile / ls -> LDS; the next tile's rows start loading
-#pragma unroll
-    for (int u = 0; u < EPT; ++u)
-        if (tid + 256 * u < BM * DP) cs[tid + 256 * u] = raw[u] / ls_e[u];
-    MPO_LOAD_TILE(tile + gridDim.x)
-    __syncthreads();
-
-    // ---- phase 1: K*[row][i] (Matern52) in A-fragment order, mu partials.  xs and
-    // alpha are zero from row n to np16 + kXsPadRows (the note above
-    // scale_rows_kernel): no bounds check on i, and the next observation row is
-    // loaded while the current one is evaluated.
+    // ---- phase 1: K*[row][i] (Matern52) in A-fragment order, mu partials.  The
+    // tile's rows were staged in cs before the last barrier (the prologue's, or the
+    // previous tile's barrier D).  xs and alpha are zero from row n to
+    // np16 + kXsPadRows (the note above scale_rows_kernel): no bounds check on i, and
+    // the next observation row is loaded while the current one is evaluated.
     {
         const int row = lane & 15;
-        const int slot = wave * 4 + (lane >> 4);
+        const int slot = vs * 4 + (lane >> 4);
         double c[D];
 #pragma unroll
         for (int q = 0; q < D; ++q) c[q] = cs[row * DP + q];
@@ -700,7 +724,7 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
                 const double* xbl = a.xb + (size_t)(lane & 15) * DP + kr;
                 double bq[DP / 4];
                 double mu4[4] = {0.0, 0.0, 0.0, 0.0};
-                for (int t = wave; t < T16; t += 4) {
+                for (int t = vs; t < T16; t += 4) {
 #pragma unroll
                     for (int s = 0; s < DP / 4; ++s) bq[s] = xbl[(size_t)t * 16 * DP + 4 * s];
                     f64x4 acc = {0.0, 0.0, 0.0, 0.0};
@@ -717,13 +741,10 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
                 }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) mu4[r] = colsum16(mu4[r]);
-                // this wave's 4 slots: the sum in slot 0, zeros in 1..3 (the mu fold below
-                // sums all 16 slots in order)
+                // the share's row of this tile's mu partials
                 if ((lane & 15) == 0) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r)
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) red[(wave * 4 + q) * BM + kr + 4 * r] = q == 0 ? mu4[r] : 0.0;
+                    for (int r = 0; r < 4; ++r) redm[vs * BM + kr + 4 * r] = mu4[r];
                 }
             }
         }
@@ -736,20 +757,31 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
                 MPO_EI_PAIR(xr, a.alpha[i], i)
             }
         }
-        if (!md || (a.dbg & 2)) red[slot * BM + row] = mu_acc;
+        if (!md || (a.dbg & 2)) {
+            // the share's 4 slots (lane >> 4) into one row
+            mu_acc += __shfl_xor(mu_acc, 16);
+            mu_acc += __shfl_xor(mu_acc, 32);
+            if (lane < BM) redm[vs * BM + row] = mu_acc;
+        }
     }
+    // Barrier B: K* complete.  It also orders two reuses that need no barrier of
+    // their own.  (1) Every read of cs (phase 1's c and af) is behind it, so the
+    // next tile's rows go into cs right below; barrier D publishes them.  (2) The q
+    // partials below overwrite redq, which wave fw read for the previous tile: fw
+    // did so before it arrived here.  The mu rows written above need no guard at
+    // all: they went to this tile's parity half of red, and what fw may still have
+    // been reading when a run-ahead wave wrote them is the other half.
     __syncthreads();
-    double mu_n = 0.0;
-    if (wave == fw && lane < BM) {
-#pragma unroll
-        for (int s = 0; s < S; ++s) mu_n += red[s * BM + lane];
-        mu_n *= a.amp;
-    }
-    __syncthreads();  // red is reused for the q partials below
+
+    // ---- the next tile's rows (in raw since the previous tile) -> cs; the one
+    // after starts loading and is not waited for before the next tile's barrier B
+    MPO_STAGE_TILE
+    MPO_LOAD_TILE(tile + 2 * (long long)gridDim.x)
 
     // ---- phase 2: V = K* L^-T on f64 MFMA, lower-triangular k-steps only.  The
     // wave walks its B-fragment stream (wave_plan_kernel) two 4-k-step groups ahead
-    // (loading the ring's first groups before the mu barriers instead measured the same).
+    // (in the four-barrier loop, loading the ring's first groups before the barriers
+    // instead measured the same).
     {
         double b0[4], b1[4];
         MPO_LD4(b0, bs);
@@ -792,20 +824,33 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const double v = colsum16(sq[r]);
-            if ((lane & 15) == 0) red[wave * BM + (lane >> 4) + 4 * r] = v;
+            if ((lane & 15) == 0) redq[wave * BM + (lane >> 4) + 4 * r] = v;
         }
     }
+    // Barrier D: every wave is done with K* (the next phase 1 rewrites kc), and the
+    // mu and q partials and the next tile's cs are visible.  The waves other than fw
+    // run ahead into the next tile's phase 1 while fw reads red below: they write
+    // only the other parity's mu rows there, and stop at barrier B, which fw reaches
+    // after its reads; redq is next written behind that barrier, and this parity's
+    // mu rows two tiles on, behind the next barrier D.
     __syncthreads();
 
-    // ---- phase 3: (mu_n, q) rows out (wave fw; the other waves go on to the next
-    // tile's phase 0 and meet wave fw at its barrier, after which red may be rewritten)
+    // ---- phase 3: (mu_n, q) rows out (wave fw): the 4 shares' mu rows and the 4
+    // waves' q rows, each folded in a fixed order
     if (wave == fw && lane < BM && m0 + lane < a.m) {
-        const double q = (red[0 * BM + lane] + red[1 * BM + lane] + red[2 * BM + lane] + red[3 * BM + lane]) *
+        double mu_n = 0.0;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) mu_n += redm[s * BM + lane];
+        mu_n *= a.amp;
+        const double q = (redq[0 * BM + lane] + redq[1 * BM + lane] + redq[2 * BM + lane] + redq[3 * BM + lane]) *
                          (a.amp * a.amp);
         *reinterpret_cast<double2*>(a.mq + 2 * (m0 + lane)) = double2{mu_n, q};
     }
+    vs = (vs + 1) & 3;
+    redm = redm == red ? red + 4 * BM : red;
     }  // tile loop
     if constexpr (FIN) score_finish_own_rows(kc, wave, lane);
+#undef MPO_STAGE_TILE
 #undef MPO_LOAD_TILE
 }
 
