@@ -125,6 +125,33 @@ int mpo_gp_prepare(const double* X, const double* y_norm, int n, int d, const do
                    double amp, double noise, double y_mean, double y_std,
                    MpoGpModel* model, void* ws, size_t ws_bytes, void* stream);
 
+/* Extend a prepared posterior by one observation at the SAME hyper-parameters: the
+ * model of n + 1 points from the model of n in O(n^2), no factorisation.  With
+ * k* = amp*Matern52(|xs_i - xs_new|), l = W k* and delta^2 = amp + noise + 1e-10 - |l|^2:
+ *   L' = [L 0; l^T delta]    W' = [W 0; -(1/delta) l^T W  1/delta]    alpha' = W'^T W' y_norm
+ * then the same packing, scoring-path choice and xb self-check as mpo_gp_prepare, into
+ * the same workspace layout (`ws` sized by mpo_gp_prepare_ws_bytes(n + 1, d)), so an
+ * appended model scores, exports and appends again like a prepared one.  Every sum
+ * runs in a fixed order (the rule of mpo_gp_prepare's blocked factorisation).
+ *   base    a prepared model of n observations (mpo_gp_prepare or an earlier append);
+ *           its workspace is only read and must stay alive until this call's work on
+ *           `stream` is done.  amp, d and dp are taken from it.
+ *   X       [n+1][d] device: the base's n observations, then the new point
+ *   y_norm  [n+1] device: the targets re-normalised over all n + 1 values (y_mean, y_std)
+ *   ls, noise  the length scales [d] (device) and noise the base was built with
+ * *info of the new model: the base's when that is non-zero, else n + 1 when delta^2 is
+ * not positive and finite (the value mpo_chol_f64 reports for that column).
+ * n + 1 > 2048 returns MPO_ENOTSUP; a null pointer, a malformed base, a workspace that
+ * is too small or is the base's own returns MPO_EINVAL.  Only enqueues work: no
+ * allocation, no host synchronisation, capturable in a graph.
+ * NOT the reference's semantics: skopt's constant-liar ask (Coordinator.ask,
+ * coordinator.py:46-50 -> Optimizer.ask(n_points)) refits the hyper-parameters for
+ * every lie; this entry point serves the opt-in fixed-theta batch
+ * (Optimizer(lie_refit="never")). */
+int mpo_gp_append(const MpoGpModel* base, const double* X, const double* y_norm,
+                  const double* ls, double noise, double y_mean, double y_std,
+                  MpoGpModel* model, void* ws, size_t ws_bytes, void* stream);
+
 /* Workspace bytes for mpo_gp_lml_grad (n <= 2048, d <= 32, batch thetas); 0 if unsupported. */
 size_t mpo_gp_lml_ws_bytes(int n, int d, int batch);
 

@@ -88,6 +88,8 @@ SIGNATURES = {
     "mpo_trsm_f64": (_I, [_P, _I, _I, _P, _I, _I, _I, _P]),
     "mpo_gp_prepare_ws_bytes": (_SZ, [_I, _I]),
     "mpo_gp_prepare": (_I, [_P, _P, _I, _I, _P, _D, _D, _D, _D, ctypes.POINTER(MpoGpModel), _P, _SZ, _P]),
+    "mpo_gp_append": (_I, [ctypes.POINTER(MpoGpModel), _P, _P, _P, _D, _D, _D, ctypes.POINTER(MpoGpModel), _P, _SZ,
+                           _P]),
     "mpo_gp_lml_ws_bytes": (_SZ, [_I, _I, _I]),
     "mpo_gp_lml_grad": (_I, [_P, _P, _I, _I, _P, _I, _P, _P, _P, _P, _SZ, _P]),
     "mpo_gp_lml_io_bytes": (_SZ, [_I, _I]),

@@ -396,7 +396,8 @@ def merge_topk(parts, k):
 
 KIND_EXIT, KIND_TRAIN, KIND_CHAINS, KIND_SCORE = 0, 1, 2, 3
 ACQ_ORDER = ("EI", "LCB", "PI")
-STATS_SCALARS = ("refits", "n_sum", "n_max", "refit_s", "propose_s", "prepare_s", "score_s", "polish_s")
+STATS_SCALARS = ("refits", "n_sum", "n_max", "refit_s", "propose_s", "prepare_s", "score_s", "polish_s",
+                 "appends")
 
 
 def encode_histories(res):
@@ -665,7 +666,7 @@ class DistributedEvaluator:
             row = part[0]
             ns = int(row[len(STATS_SCALARS)])
             d_ = {k_: row[j] for j, k_ in enumerate(STATS_SCALARS)}
-            for k_ in ("refits", "n_sum", "n_max"):
+            for k_ in ("refits", "n_sum", "n_max", "appends"):
                 d_[k_] = int(d_[k_])
             smp = row[len(STATS_SCALARS) + 1:len(STATS_SCALARS) + 1 + 2 * ns].reshape(ns, 2)
             d_["samples"] = [(int(a), float(b)) for a, b in smp]

@@ -7,6 +7,7 @@
 // Kernels
 //   scale_rows_kernel    xs = X / ls (dims zero-padded to DP)
 //   bc_*_kernel          blocked K = L L^T, W = L^-1, alpha (mpo_gp_prepare)
+//   ap_*_kernel          rank-one append of one observation at fixed theta (mpo_gp_append)
 //   chol_kernel          in-place lower Cholesky (one workgroup; mpo_chol_f64)
 //   trsm_kernel          L X = B / L^T X = B, one thread per right-hand side (mpo_trsm_f64)
 //   pack_wfrag_kernel    L^-1 -> MFMA B-fragment stream (lower triangle only)
@@ -1555,6 +1556,90 @@ hipError_t blocked_factor(const double* xs, int n, int dp, double amp, double di
 }
 
 // ---------------------------------------------------------------------------
+// Rank-one append for mpo_gp_append: the factor of n + 1 observations from the factor
+// of n at the same hyper-parameters.  With k* = K(X, x_new), l = W k* (W = L^-1) and
+// delta^2 = K(x_new, x_new) - |l|^2:
+//   L' = [L 0; l^T delta]     W' = [W 0; -(1/delta) l^T W   1/delta]
+// l and l^T W are bc_wy_kernel / bc_wtv_kernel on the old W (leading dimension n), so
+// every sum runs in the fixed order of the blocked factorisation; what is new here is
+// k*, delta and the copy of both triangles to the leading dimension n + 1.
+
+// k*_i = amp Matern52(|xs_i - xs_n|), i < n: row n of bc_kmat_kernel's matrix
+__global__ void ap_kstar_kernel(const double* __restrict__ xs, int n, int dp, double amp, double* __restrict__ ks) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    double r2 = 0.0;
+    for (int c = 0; c < dp; ++c) {
+        const double t = xs[(size_t)n * dp + c] - xs[(size_t)j * dp + c];
+        r2 += t * t;
+    }
+    ks[j] = matern52(sqrt(r2), amp);
+}
+
+// One workgroup: dl = (delta, 1 / delta) from delta^2 = kdiag - sum l_i^2 (thread t sums
+// i = t, t + 256, ... in order, a fixed butterfly per wave, the four waves in order), and
+// the new model's info: the base's when that failed, else n + 1 (the column mpo_chol_f64
+// reports) for a non-positive or non-finite pivot.
+__global__ __launch_bounds__(256) void ap_delta_kernel(const double* __restrict__ l, int n, double kdiag,
+                                                       const int32_t* __restrict__ base_info,
+                                                       double* __restrict__ dl, int32_t* __restrict__ info) {
+    __shared__ double red[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) s = fma(l[i], l[i], s);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double d2 = kdiag - (((red[0] + red[1]) + red[2]) + red[3]);
+        const bool bad = !(d2 > 0.0) || !isfinite(d2);
+        const double dlt = sqrt(d2);
+        dl[0] = dlt;
+        dl[1] = 1.0 / dlt;
+        const int32_t bi = base_info[0];
+        info[0] = bi ? bi : bad ? n + 1 : 0;
+    }
+}
+
+// Both triangles at the new leading dimension n + 1 (zeros above the diagonal): rows
+// i < n from the base, row n = (l^T, delta) of L and (-(1/delta) t^T, 1/delta) of W,
+// t = W^T l.
+__global__ void ap_copy_kernel(const double* __restrict__ L0, const double* __restrict__ W0, int n,
+                               const double* __restrict__ l, const double* __restrict__ t,
+                               const double* __restrict__ dl, double* __restrict__ L, double* __restrict__ W) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = blockIdx.y;
+    const int n1 = n + 1;
+    if (j >= n1) return;
+    double lv, wv;
+    if (i < n) {
+        lv = j <= i ? L0[(size_t)i * n + j] : 0.0;
+        wv = j <= i ? W0[(size_t)i * n + j] : 0.0;
+    } else {
+        lv = j < n ? l[j] : dl[0];
+        wv = j < n ? -dl[1] * t[j] : dl[1];
+    }
+    L[(size_t)i * n1 + j] = lv;
+    W[(size_t)i * n1 + j] = wv;
+}
+
+// The launch sequence of the append (+ alpha) on stream s; sc: 3 (n + 1) + 2 doubles of scratch.
+hipError_t append_factor(const double* xs, int n, int dp, double amp, double diag_add, const double* y_norm,
+                         const double* L0, const double* W0, const int32_t* info0, double* sc, double* v, double* L,
+                         double* W, double* alpha, int32_t* info, hipStream_t s) {
+    const int n1 = n + 1;
+    double *ks = sc, *l = sc + n1, *t = sc + 2 * (size_t)n1, *dl = sc + 3 * (size_t)n1;
+    hipLaunchKernelGGL(ap_kstar_kernel, dim3((n + 255) / 256), dim3(256), 0, s, xs, n, dp, amp, ks);
+    hipLaunchKernelGGL(bc_wy_kernel, dim3((n + 3) / 4), dim3(256), 0, s, W0, n, n, ks, l);
+    hipLaunchKernelGGL(ap_delta_kernel, dim3(1), dim3(256), 0, s, l, n, amp + diag_add, info0, dl, info);
+    hipLaunchKernelGGL(bc_wtv_kernel, dim3((n + 255) / 256), dim3(256), 0, s, W0, n, n, l, t);
+    hipLaunchKernelGGL(ap_copy_kernel, dim3((n1 + 63) / 64, n1), dim3(64), 0, s, L0, W0, n, l, t, dl, L, W);
+    hipLaunchKernelGGL(bc_wy_kernel, dim3((n1 + 3) / 4), dim3(256), 0, s, W, n1, n1, y_norm, v);
+    hipLaunchKernelGGL(bc_wtv_kernel, dim3((n1 + 255) / 256), dim3(256), 0, s, W, n1, n1, v, alpha);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // Acquisition value + gradient at a few points: the objective of skopt's
 // L-BFGS-B polish of the best n_restarts_optimizer candidates per acquisition
 // (skopt optimizer.py _tell -> fmin_l_bfgs_b(gaussian_acquisition_1D, ...,
@@ -1815,6 +1900,68 @@ inline ScoreArgs model_score_args(const MpoGpModel& md) {
     return a;
 }
 
+// The model's pointers into its carved workspace (xb: finish_prepared, once the self-check ran)
+inline void point_model(MpoGpModel& md, const PrepareWs& w) {
+    md.xs = w.xs;
+    md.ls = w.ls_pad;
+    md.alpha = w.alpha;
+    md.wfrag = w.wfrag;
+    md.L = w.L;
+    md.W = w.W;
+    md.info = w.info;
+    md.wmeta = w.wmeta;
+    md.xb = nullptr;
+}
+
+// The tail of a prepared model, shared by mpo_gp_prepare and mpo_gp_append: L^-1 packed for
+// the scoring kernel and, on the resident path with d + 2 <= dp, xb and its self-check.
+// md: everything but xb set; X: the model's n observations (the self-check's candidates).
+int finish_prepared(MpoGpModel& md, const PrepareWs& w, const ScorePlan& plan, const double* X, hipStream_t s) {
+    const int n = md.n, d = md.d, dp = md.dp, np16 = md.np16;
+    const int xrows = np16 + kXsPadRows;
+    const double amp = md.amp;
+    const int T = np16 / 16;
+    const size_t nw = wfrag_elems(np16);
+    hipLaunchKernelGGL(zero_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w.wfrag, (int)nw);
+    MPO_LAUNCH_CHECK();
+    hipLaunchKernelGGL(wave_plan_kernel, dim3(1), dim3(64), 0, s, T, w.wmeta);
+    MPO_LAUNCH_CHECK();
+    hipLaunchKernelGGL(pack_wfrag_kernel, dim3((4 * T * 64 + 255) / 256, T), dim3(256), 0, s, w.W, n, n, T, w.wmeta,
+                       w.wfrag);
+    MPO_LAUNCH_CHECK();
+    // The expanded (MFMA) distance |c|^2 + |x|^2 - 2 c.x (d + 2 <= dp) carries an absolute
+    // error of a few eps (|c|^2 + |x|^2) instead of the direct form's eps r2.  Its device
+    // flag is set only when every |x|^2 <= kDistNorm and, scoring the observations
+    // themselves both ways, (mu_n, q) agree within 1e-10; candidate tiles with some
+    // |c|^2 > kDistNorm take the direct form in the kernel.  MPO_GP_DIST=0: never.
+    const char* de = getenv("MPO_GP_DIST");
+    // A streamed model (score_plan) always scores with the direct form: no xb, no self-check.
+    if (plan.path == 0 && d + 2 <= dp && !(de && de[0] == '0')) {
+        double* flag = xb_flag(w.xb, np16, dp);
+        hipLaunchKernelGGL(xb_kernel, dim3(1), dim3(256), 0, s, w.xs, xrows, d, dp, w.xb);
+        MPO_LAUNCH_CHECK();
+        ScoreArgs sa = model_score_args(md);           // md.xb still null: the direct form
+        sa.cand = X;
+        sa.m = n;
+        sa.flags = 1;
+        const int nt = (n + kBM - 1) / kBM;
+        double* mqm = w.mqc + 2 * (size_t)n;
+        sa.mq = w.mqc;
+        bool ok = launch_scoring(dp, d, plan, sa, nt, s, /*fin=*/false) == hipSuccess;
+        sa.mq = mqm;                                   // expanded form
+        sa.xb = w.xb;
+        sa.xb_ok = flag;
+        // a refused variant (MPO_GP_OCC forcing a spilling one) just leaves xb out
+        ok = ok && launch_scoring(dp, d, plan, sa, nt, s, /*fin=*/false) == hipSuccess;
+        if (ok) {
+            hipLaunchKernelGGL(xb_check_kernel, dim3(1), dim3(256), 0, s, w.mqc, mqm, w.alpha, n, amp, flag);
+            MPO_LAUNCH_CHECK();
+            md.xb = w.xb;
+        }
+    }
+    return MPO_OK;
+}
+
 }  // namespace
 
 // ===========================================================================
@@ -1880,15 +2027,7 @@ int mpo_gp_prepare(const double* X, const double* y_norm, int n, int d, const do
     ScorePlan plan;
     if (const int rc = score_plan("mpo_gp_prepare", &md, n, &plan)) return rc;
     const PrepareWs w = carve_prepare_ws(ws, n, dp);
-    md.xs = w.xs;
-    md.ls = w.ls_pad;
-    md.alpha = w.alpha;
-    md.wfrag = w.wfrag;
-    md.L = w.L;
-    md.W = w.W;
-    md.info = w.info;
-    md.wmeta = w.wmeta;
-    md.xb = nullptr;   // set below once the self-check has run
+    point_model(md, w);
     hipStream_t s = static_cast<hipStream_t>(stream);
 
     hipLaunchKernelGGL(scale_rows_kernel, dim3((xrows * dp + 255) / 256), dim3(256), 0, s, X, n, xrows, d, dp, ls, w.xs,
@@ -1898,45 +2037,51 @@ int mpo_gp_prepare(const double* X, const double* y_norm, int n, int d, const do
     MPO_LAUNCH_CHECK();
     MPO_HIP(blocked_factor(w.xs, n, dp, amp, noise + kJitter, y_norm, w.Ab, w.Wb, w.Db, w.vb, w.L, w.W, w.alpha, w.info,
                            s));
-    const int T = np16 / 16;
-    const size_t nw = wfrag_elems(np16);
-    hipLaunchKernelGGL(zero_kernel, dim3((unsigned)((nw + 255) / 256)), dim3(256), 0, s, w.wfrag, (int)nw);
-    MPO_LAUNCH_CHECK();
-    hipLaunchKernelGGL(wave_plan_kernel, dim3(1), dim3(64), 0, s, T, w.wmeta);
-    MPO_LAUNCH_CHECK();
-    hipLaunchKernelGGL(pack_wfrag_kernel, dim3((4 * T * 64 + 255) / 256, T), dim3(256), 0, s, w.W, n, n, T, w.wmeta,
-                       w.wfrag);
-    MPO_LAUNCH_CHECK();
-    // The expanded (MFMA) distance |c|^2 + |x|^2 - 2 c.x (d + 2 <= dp) carries an absolute
-    // error of a few eps (|c|^2 + |x|^2) instead of the direct form's eps r2.  Its device
-    // flag is set only when every |x|^2 <= kDistNorm and, scoring the observations
-    // themselves both ways, (mu_n, q) agree within 1e-10; candidate tiles with some
-    // |c|^2 > kDistNorm take the direct form in the kernel.  MPO_GP_DIST=0: never.
-    const char* de = getenv("MPO_GP_DIST");
-    // A streamed model (score_plan) always scores with the direct form: no xb, no self-check.
-    if (plan.path == 0 && d + 2 <= dp && !(de && de[0] == '0')) {
-        double* flag = xb_flag(w.xb, np16, dp);
-        hipLaunchKernelGGL(xb_kernel, dim3(1), dim3(256), 0, s, w.xs, xrows, d, dp, w.xb);
-        MPO_LAUNCH_CHECK();
-        ScoreArgs sa = model_score_args(md);           // md.xb still null: the direct form
-        sa.cand = X;
-        sa.m = n;
-        sa.flags = 1;
-        const int nt = (n + kBM - 1) / kBM;
-        double* mqm = w.mqc + 2 * (size_t)n;
-        sa.mq = w.mqc;
-        bool ok = launch_scoring(dp, d, plan, sa, nt, s, /*fin=*/false) == hipSuccess;
-        sa.mq = mqm;                                   // expanded form
-        sa.xb = w.xb;
-        sa.xb_ok = flag;
-        // a refused variant (MPO_GP_OCC forcing a spilling one) just leaves xb out
-        ok = ok && launch_scoring(dp, d, plan, sa, nt, s, /*fin=*/false) == hipSuccess;
-        if (ok) {
-            hipLaunchKernelGGL(xb_check_kernel, dim3(1), dim3(256), 0, s, w.mqc, mqm, w.alpha, n, amp, flag);
-            MPO_LAUNCH_CHECK();
-            md.xb = w.xb;
-        }
+    if (const int rc = finish_prepared(md, w, plan, X, s)) return rc;
+    *model = md;
+    return MPO_OK;
+    MPO_GUARD_END
+}
+
+int mpo_gp_append(const MpoGpModel* base, const double* X, const double* y_norm, const double* ls, double noise,
+                  double y_mean, double y_std, MpoGpModel* model, void* ws, size_t ws_bytes, void* stream) {
+    MPO_GUARD_BEGIN
+    MPO_CHECK_ARG(base && X && y_norm && ls && model && ws, "mpo_gp_append: null pointer");
+    const int n = base->n, d = base->d, dp = base->dp, n1 = n + 1;
+    MPO_CHECK_ARG(n > 0 && d > 0 && dp > 0 && pad_dims(d) == dp, "mpo_gp_append: malformed base model n=%d d=%d dp=%d",
+                  n, d, dp);
+    if (n1 > mpo::kMaxObs) {
+        mpo::set_error("mpo_gp_append: n=%d exceeds the supported maximum of %d observations", n1, mpo::kMaxObs);
+        return MPO_ENOTSUP;
     }
+    MPO_CHECK_ARG(ws_bytes >= mpo_gp_prepare_ws_bytes(n1, d), "mpo_gp_append: workspace too small (%zu < %zu)",
+                  ws_bytes, mpo_gp_prepare_ws_bytes(n1, d));
+    MPO_CHECK_ARG(base->L && base->W && base->info, "mpo_gp_append: base model not prepared");
+    const int np16 = (n1 + 15) / 16 * 16;
+    const int xrows = np16 + kXsPadRows;
+    MpoGpModel md{};
+    md.n = n1;
+    md.d = d;
+    md.dp = dp;
+    md.np16 = np16;
+    md.amp = base->amp;
+    md.y_mean = y_mean;
+    md.y_std = y_std;
+    ScorePlan plan;
+    if (const int rc = score_plan("mpo_gp_append", &md, n1, &plan)) return rc;
+    const PrepareWs w = carve_prepare_ws(ws, n1, dp);
+    MPO_CHECK_ARG(w.xs != base->xs, "mpo_gp_append: ws is the base model's workspace (the append is not in place)");
+    point_model(md, w);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+
+    hipLaunchKernelGGL(scale_rows_kernel, dim3((xrows * dp + 255) / 256), dim3(256), 0, s, X, n1, xrows, d, dp, ls, w.xs,
+                       w.ls_pad);
+    MPO_LAUNCH_CHECK();
+    hipLaunchKernelGGL(zero_kernel, dim3((xrows + 255) / 256), dim3(256), 0, s, w.alpha, xrows);
+    MPO_LAUNCH_CHECK();
+    MPO_HIP(append_factor(w.xs, n, dp, md.amp, noise + kJitter, y_norm, base->L, base->W, base->info, w.Db, w.vb, w.L,
+                          w.W, w.alpha, w.info, s));
+    if (const int rc = finish_prepared(md, w, plan, X, s)) return rc;
     *model = md;
     return MPO_OK;
     MPO_GUARD_END

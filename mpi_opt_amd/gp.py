@@ -47,12 +47,7 @@ class DeviceGP:
             raise ValueError(f"bad GP data shapes X={X.shape} y={y.shape}")
         n, d = X.shape
         ls = np.broadcast_to(np.asarray(length_scale, dtype=np.float64), (d,)).copy()
-        # normalize_y=True (sklearn _gpr.py:273-277)
-        y_mean = float(np.mean(y))
-        y_std = float(np.std(y))
-        if y_std == 0.0:
-            y_std = 1.0
-        y_norm = (y - y_mean) / y_std
+        y_mean, y_std, y_norm = _normalise(y)
         self.n, self.d = n, d
         self.amp, self.noise = float(amp), float(noise)
         self.length_scale = ls
@@ -77,6 +72,47 @@ class DeviceGP:
             raise np.linalg.LinAlgError(
                 f"device Cholesky failed at column {self.chol_info - 1} (K not positive definite)")
         self._score_ws = None
+
+    def appended(self, x_new, y_all):
+        """``mpo_gp_append``: a new DeviceGP of this model's n observations plus ``x_new``
+        (d,), at the same hyper-parameters, from this model's factor in O(n^2) -- no
+        factorisation.  ``y_all`` (n + 1,) are the raw targets of all points (a constant-liar
+        lie changes the normalisation: ``y_mean`` / ``y_std`` are recomputed as ``__init__``
+        does).  This model is only read and stays usable.  Raises ``LinAlgError`` on a
+        non-zero info, as ``__init__`` does."""
+        if not hasattr(self, "_X"):
+            raise ValueError("a scoring-only DeviceGP (from_factor) holds no observations to append to")
+        x_new = np.asarray(x_new, dtype=np.float64).reshape(-1)
+        y = np.asarray(y_all, dtype=np.float64).reshape(-1)
+        n, d = self.n + 1, self.d
+        if x_new.shape[0] != d or y.shape[0] != n:
+            raise ValueError(f"bad append shapes x_new={x_new.shape} y_all={y.shape} for n={self.n} d={d}")
+        y_mean, y_std, y_norm = _normalise(y)
+        g = DeviceGP.__new__(DeviceGP)
+        g.device = self.device
+        g.n, g.d = n, d
+        g.amp, g.noise, g.length_scale = self.amp, self.noise, self.length_scale
+        g.y_mean, g.y_std, g.y = y_mean, y_std, y
+        L = lib()
+        g._X = torch.cat([self._X, torch.from_numpy(x_new).to(self.device).view(1, d)])
+        g._y = torch.from_numpy(y_norm).to(self.device)
+        g._ls = self._ls
+        wsb = L.mpo_gp_prepare_ws_bytes(n, d)
+        if wsb == 0:
+            raise _lib.MpoError(f"unsupported GP shape n={n} d={d} (n <= 2048, d <= 32)")
+        g._ws = torch.empty(wsb, dtype=torch.uint8, device=self.device)
+        g.model = _lib.MpoGpModel()
+        with torch.cuda.device(self.device):
+            s = _lib.stream_handle(self.device)
+            check(L.mpo_gp_append(ctypes.byref(self.model), ptr(g._X), ptr(g._y), ptr(g._ls), self.noise, y_mean,
+                                  y_std, ctypes.byref(g.model), ptr(g._ws), wsb, s), "mpo_gp_append")
+        # the read of info waits for the append: this model's workspace is free again after it
+        g.chol_info = int(_view_int32(g.model.info, g._ws, g.device).item())
+        if g.chol_info != 0:
+            raise np.linalg.LinAlgError(
+                f"device Cholesky failed at column {g.chol_info - 1} (K not positive definite)")
+        g._score_ws = None
+        return g
 
     # -- the prepared factor as plain arrays (the sharded scorer's broadcast) ----
     _PTRS = ("xs", "ls", "alpha", "wfrag", "L", "W", "info", "wmeta", "xb")
@@ -269,6 +305,15 @@ class DeviceGP:
         mu = out["mu"].cpu().numpy()
         sd = out["sd"].cpu().numpy()
         return (mu, sd) if return_std else mu
+
+
+def _normalise(y):
+    """normalize_y=True (sklearn _gpr.py:273-277): (y_mean, y_std, y_norm)."""
+    y_mean = float(np.mean(y))
+    y_std = float(np.std(y))
+    if y_std == 0.0:
+        y_std = 1.0
+    return y_mean, y_std, (y - y_mean) / y_std
 
 
 def _view_int32(addr, ws, device):

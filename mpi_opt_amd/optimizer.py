@@ -79,6 +79,16 @@ class GPModel:
             self._dev = DeviceGP(self.Xt, self.y, self.amp, self.length_scale, self.noise, device=self.device)
         return self._dev
 
+    def appended(self, x_t, y_all):
+        """The surrogate of this model's points plus ``x_t`` (transformed space) at the
+        SAME hyper-parameters, its device posterior extended from this one's by
+        ``DeviceGP.appended`` (``mpo_gp_append``: no refit, no factorisation).  ``y_all``
+        are the targets of all n + 1 points.  The one place the optimizer appends."""
+        Xt = np.vstack([self.Xt, np.asarray(x_t, dtype=float).reshape(1, -1)])
+        est = GPModel(Xt, y_all, self.amp, self.length_scale, self.noise, device=self.device)
+        est._dev = self.dev.appended(Xt[-1], est.y)
+        return est
+
     def predict_mean(self, X):
         mu, _ = self.dev.predict(np.atleast_2d(X))
         return mu
@@ -135,15 +145,17 @@ def polish_lockstep(model, starts, acqs, y_opt, xi, kappa, bounds, maxiter=20, d
 #: observation counts and the seconds spent refitting vs proposing.  Chains run
 #: on worker threads (:mod:`~mpi_opt_amd.chains`), so updates take ``STATS_LOCK``;
 #: the seconds are then summed over concurrent workers (device-thread seconds).
+#: ``refits`` counts proposals; ``appends`` those of them whose model came from a
+#: fixed-theta append (``lie_refit="never"``: no refit seconds, the append under prepare_s).
 STATS = {"refits": 0, "n_sum": 0, "n_max": 0, "refit_s": 0.0, "propose_s": 0.0, "prepare_s": 0.0, "score_s": 0.0,
-         "polish_s": 0.0, "samples": []}
+         "polish_s": 0.0, "appends": 0, "samples": []}
 STATS_LOCK = threading.Lock()
 
 
 def reset_stats():
     with STATS_LOCK:
         STATS.update(refits=0, n_sum=0, n_max=0, refit_s=0.0, propose_s=0.0, prepare_s=0.0, score_s=0.0,
-                     polish_s=0.0, samples=[])
+                     polish_s=0.0, appends=0, samples=[])
 
 
 def merge_stats(delta):
@@ -158,9 +170,10 @@ def merge_stats(delta):
                 STATS[k] += v
 
 
-def _record_refit(n, t_refit, t_prepare, t_score, t_polish, t_propose, t_total):
+def _record_refit(n, t_refit, t_prepare, t_score, t_polish, t_propose, t_total, append=False):
     with STATS_LOCK:
         STATS["refits"] += 1
+        STATS["appends"] += int(append)
         STATS["n_sum"] += n
         STATS["n_max"] = max(STATS["n_max"], n)
         STATS["refit_s"] += t_refit
@@ -172,6 +185,9 @@ def _record_refit(n, t_refit, t_prepare, t_score, t_polish, t_propose, t_total):
 
 
 STRATEGIES = ("cl_min", "cl_mean", "cl_max")
+#: Optimizer(lie_refit=...): refit the hyper-parameters for every lie of an ask(n) batch
+#: (skopt) or for none of them
+LIE_REFIT = ("every", "never")
 
 #: the most observations one GP takes (the refit's and the scoring kernels' bound in libmpo.so)
 MAX_GP_POINTS = 2048
@@ -291,8 +307,11 @@ class ChainJob:
 
 
 def _lie_loop(opt, n_points, strategy):
-    """skopt's constant-liar loop on the copy ``opt``: ask, then tell the lie."""
+    """skopt's constant-liar loop on the copy ``opt``: ask, then tell the lie.  With
+    ``lie_refit="never"`` (not skopt's semantics) a lie told to a copy that has a
+    fitted model keeps that model's hyper-parameters and appends the point to it."""
     X = []
+    append = opt.lie_refit == "never"
     for _ in range(n_points):
         x = opt._ask()
         X.append(x)
@@ -302,7 +321,7 @@ def _lie_loop(opt, n_points, strategy):
             lie = np.mean(opt.yi) if opt.yi else 0.0
         else:
             lie = np.max(opt.yi) if opt.yi else 0.0
-        opt._tell(x, lie)
+        opt._tell(x, lie, append=append)
         # only the newest surrogate is used again (gains, the next proposal):
         # release the older ones' device factorisations as the chain grows
         for m in opt.models[:-1]:
@@ -322,12 +341,24 @@ class Optimizer:
 
     ``acq_optimizer_kwargs["n_restarts_optimizer"]`` (default 5) may exceed the
     device top-k width (``MPO_TOPK_MAX`` = 8); the acquisition rows are then
-    sorted whole on the device instead."""
+    sorted whole on the device instead.
+
+    ``lie_refit`` ("every" | "never", an addition of this build): "every" is skopt's
+    ``ask(n)``, a hyper-parameter refit per constant-liar lie.  "never" departs from it:
+    the lies of a batch keep the theta of the copy's newest model and extend its
+    posterior by one observation each (``mpo_gp_append``, O(n^2)); a copy without a
+    model does one full fit first.  ``tell`` on the asking optimizer always refits."""
 
     def __init__(self, dimensions, base_estimator="gp", n_random_starts=None, n_initial_points=10,
                  initial_point_generator="random", acq_func="gp_hedge", acq_optimizer="auto",
                  random_state=None, model_queue_size=None, acq_func_kwargs=None, acq_optimizer_kwargs=None,
-                 device=None, _gp_seed=None, scorer=None, chain_executor=None):
+                 device=None, _gp_seed=None, scorer=None, chain_executor=None, lie_refit="every"):
+        if lie_refit not in LIE_REFIT:
+            raise ValueError(f"lie_refit {lie_refit!r}: one of {LIE_REFIT}")
+        # "every": skopt's ask(n) -- a hyper-parameter refit per constant-liar lie.  "never"
+        # (NOT the reference's semantics): the batch keeps the theta of the copy's model and
+        # extends its posterior by one observation per lie (GPModel.appended).
+        self.lie_refit = lie_refit
         self.rng = check_random_state(random_state)
         self.space = Space(dimensions)
         if n_random_starts is not None:
@@ -375,6 +406,7 @@ class Optimizer:
         # checkpoints written before these attributes existed resume with their defaults
         d.setdefault("trace", None)
         d.setdefault("chain_executor", None)
+        d.setdefault("lie_refit", "every")
         self.__dict__.update(d)
 
     def _config(self):
@@ -382,7 +414,8 @@ class Optimizer:
         return dict(dimensions=self.space.dimensions, base_estimator=self.base_estimator_,
                     n_initial_points=self.n_initial_points_, initial_point_generator=self._initial_point_generator,
                     acq_func=self.acq_func, acq_optimizer=self.acq_optimizer, acq_func_kwargs=self.acq_func_kwargs,
-                    acq_optimizer_kwargs=self.acq_optimizer_kwargs, _gp_seed=self._gp_seed)
+                    acq_optimizer_kwargs=self.acq_optimizer_kwargs, _gp_seed=self._gp_seed,
+                    lie_refit=self.lie_refit)
 
     # ---- ask -------------------------------------------------------------------
     def copy(self, random_state=None):
@@ -429,7 +462,7 @@ class Optimizer:
                 raise ValueError("tell: X and y must have matching lengths")
         return self._tell(x, y, fit=fit)
 
-    def _tell(self, x, y, fit=True):
+    def _tell(self, x, y, fit=True, append=False):
         batch = len(x) and isinstance(x[0], (list, tuple, np.ndarray))
         n_new = len(y) if batch else 1
         if fit and self._n_initial_points - n_new <= 0 and self.base_estimator_ == "gp":
@@ -444,7 +477,12 @@ class Optimizer:
             self._n_initial_points -= 1
         self.cache_ = {}
         if fit and self._n_initial_points <= 0 and self.base_estimator_ == "gp":
-            self._fit_and_propose()
+            # a lie of a lie_refit="never" batch keeps the theta of the newest model when that
+            # holds all points but this one; a copy without a model yet does one full fit
+            if append and not batch and self.models and len(self.models[-1].y) == len(self.yi) - 1:
+                self._append_and_propose()
+            else:
+                self._fit_and_propose()
         return self._result()
 
     def _fit_and_propose(self):
@@ -455,7 +493,21 @@ class Optimizer:
         t1 = time.perf_counter()
         est = GPModel(Xt, y, amp, ls, noise, device=self.device)
         est.dev                                   # the device posterior (mpo_gp_prepare)
-        t2 = time.perf_counter()
+        self._propose(est, t0, t1, time.perf_counter())
+
+    def _append_and_propose(self):
+        """``_fit_and_propose`` without the refit: the newest model's theta, its posterior
+        extended by the last told point (``mpo_gp_append``), then the unchanged proposal."""
+        Xt = self.space.transform(self.Xi)
+        y = np.asarray(self.yi, dtype=float)
+        t0 = time.perf_counter()
+        est = self.models[-1].appended(Xt[-1], y)
+        self._propose(est, t0, t0, time.perf_counter(), append=True)
+
+    def _propose(self, est, t0, t1, t2, append=False):
+        """The proposal from a fresh surrogate ``est`` (t0 .. t1 its refit, t1 .. t2 its
+        device posterior): gp_hedge gains, candidates, top-k, polish, pick."""
+        y = est.y
         if hasattr(self, "next_xs_") and self.acq_func == "gp_hedge":
             self.gains_ -= est.predict_mean(np.vstack(self.next_xs_))
         if self.model_queue_size is None or self.model_queue_size > 0:
@@ -506,7 +558,7 @@ class Optimizer:
             self.trace.append(rec)
         self._next_x = self.space.inverse_transform(next_x.reshape(1, -1))[0]
         t5 = time.perf_counter()
-        _record_refit(len(y), t1 - t0, t2 - t1, t4 - t3, t_polish, t5 - t1, t5 - t0)
+        _record_refit(len(y), t1 - t0, t2 - t1, t4 - t3, t_polish, t5 - t1, t5 - t0, append=append)
 
     def _score_topk(self, est, X, y_opt, xi, kappa, k):
         """skopt's ``np.argsort(values)[:k]`` per acquisition (lowest index first on

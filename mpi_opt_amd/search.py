@@ -21,6 +21,11 @@ that configure mpi_learn's Downpour/EASGD exchange (--sync-every, --easgd,
 recorded but have no effect: a trial is trained synchronously on one GPU
 (single-trial semantics).  ``--preload-data`` / ``--cache-data``
 concern mpi_learn's file loader; the data here is resident in HBM.
+
+``--lie-refit never`` (an addition, default ``every``) departs from the reference:
+skopt refits the GP hyper-parameters for every constant-liar lie of an ask batch;
+``never`` keeps the theta of the last told model for the whole batch and appends
+each lie to the posterior (``mpo_gp_append``).
 """
 from __future__ import annotations
 
@@ -88,6 +93,11 @@ def make_parser():
     p.add_argument("--population-chunks", type=int, default=1, dest="population_chunks",
                    help="train each population in this many parts, each as soon as its ask batches "
                         "resolve (overlaps the remaining batches with training; results unchanged)")
+    p.add_argument("--lie-refit", default="every", choices=["every", "never"], dest="lie_refit",
+                   help="hyper-parameter refits inside an ask batch: every (a refit per constant-liar lie, "
+                        "skopt's and the reference's semantics) or never (NOT the reference's semantics: the "
+                        "batch keeps the theta of the last told model and appends each lie to its posterior "
+                        "in O(n^2); tells always refit)")
     return p
 
 
@@ -211,6 +221,8 @@ def run_search(args, x=None, y=None, log=print, progress=None, on_population=Non
 
     comm.on_population = _population_done
     opt_kw = {"device": dev, "acq_optimizer_kwargs": {"n_points": args.ei_candidates}}
+    if args.lie_refit != "every":
+        opt_kw["lie_refit"] = args.lie_refit              # fixed-theta ask batches (not skopt's semantics)
     if chains is not None:
         opt_kw["chain_executor"] = chains                 # ask batches run concurrently (mpi_opt_amd.chains)
     if dist is not None:

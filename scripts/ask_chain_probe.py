@@ -2,7 +2,10 @@
 thread, every refit at n = 256 .. 256 + N) with a shorter batch by default, plus
 the LML rounds the native L-BFGS-B driver ran per refit (DeviceLML.fit).
 
-    python scripts/ask_chain_probe.py [--ask-n 64] [--reps 2]
+    python scripts/ask_chain_probe.py [--ask-n 64] [--reps 2] [--lie-refit every|never]
+
+``--lie-refit never``: the fixed-theta batch (Optimizer(lie_refit="never"), not skopt's
+semantics): no refit per lie, each lie appended to the posterior (mpo_gp_append).
 """
 import argparse
 import os
@@ -34,10 +37,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ask-n", type=int, default=64)
     ap.add_argument("--reps", type=int, default=2)
+    ap.add_argument("--lie-refit", default="every", choices=["every", "never"], dest="lie_refit")
     a = ap.parse_args()
     for rep in range(a.reps):
         rng = np.random.RandomState(256)
-        opt = OPT.Optimizer(mnist_space(), random_state=13579, device="cuda:0")
+        kw = {"lie_refit": a.lie_refit} if a.lie_refit != "every" else {}
+        opt = OPT.Optimizer(mnist_space(), random_state=13579, device="cuda:0", **kw)
         pts = opt.space.rvs(n_samples=256, random_state=rng)
         ys = [float(((p[0] - 30) / 40) ** 2 + ((p[3] - 120) / 150) ** 2 + (p[4] - 0.3) ** 2 + 0.1 * rng.rand())
               for p in pts]
@@ -50,7 +55,10 @@ def main():
         dt = time.perf_counter() - t0
         st = dict(OPT.STATS)
         print(f"rep {rep}: ask({a.ask_n}) {dt:.3f} s, {st['refits']} refits, "
-              f"{1e3 * st['refit_s'] / st['refits']:.2f} ms/refit, {1e3 * st['propose_s'] / st['refits']:.2f} ms/proposal, "
+              f"{st.get('appends', 0)} appends, "
+              f"{1e3 * st['refit_s'] / st['refits']:.2f} ms/refit, {1e3 * st['propose_s'] / st['refits']:.2f} ms/proposal "
+              f"(prepare-or-append {1e3 * st['prepare_s'] / st['refits']:.2f}, score {1e3 * st['score_s'] / st['refits']:.2f}, "
+              f"polish {1e3 * st['polish_s'] / st['refits']:.2f}), "
               f"{ROUNDS[0] / st['refits']:.1f} LML rounds/refit ({1e6 * st['refit_s'] / max(1, ROUNDS[0]):.0f} us/round), "
               f"first point {list(batch[0])}", flush=True)
 
