@@ -238,6 +238,53 @@ int mpo_gp_acq_grad_host(const MpoGpModel* model, const double* x_host, int batc
                          double y_opt, double xi, double kappa, double* f_host, double* g_host, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Acquisition candidates drawn on the device (opt-in: Optimizer(candidates="device")).
+ * skopt draws the n_points candidates of every ask on the host, column by column from
+ * one RandomState (Space.rvs + transform, reached from Coordinator.ask,
+ * coordinator.py:46-50); that stays the default.  NOT the reference's stream: here
+ * candidate i is a pure function of (seed, i), so any slice of the set can be made on
+ * any device without being sent.
+ * ---------------------------------------------------------------------- */
+#define MPO_DIM_REAL 0
+#define MPO_DIM_INTEGER 1
+#define MPO_DIM_CATEGORICAL 2
+
+/* One dimension of the ORIGINAL search space. */
+typedef struct MpoDimDesc {
+    int32_t kind;          /* MPO_DIM_*                                                   */
+    int32_t pad;
+    int64_t count;         /* Integer: high - low (>= 0, < 2^52); Categorical: number of
+                              categories (>= 1); Real: ignored                            */
+} MpoDimDesc;
+
+/* Rows first .. first + m - 1 of the candidate set of `seed`, in the transformed space:
+ * out [m][d] fp64 row-major (device), the layout mpo_gp_acq_score takes.  Transformed
+ * widths: Real and Integer 1 column; Categorical 1 column with <= 2 categories, else one
+ * column per category.  d must equal the sum of the widths and be <= 32; n_dims 1..32.
+ * The law (fixed: tests compare bits with a numpy restatement, tests/philox_ref.py):
+ *   Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl 0x9E3779B9 / 0xBB67AE85),
+ *   key (seed low 32, seed high 32); for candidate i and the pair b of original
+ *   dimensions (2b, 2b+1) the counter is (i low 32, i high 32, b, 0) and, of the output
+ *   words r0..r3, dimension 2b takes u = u53(r0, r1) and 2b+1 takes u = u53(r2, r3),
+ *   u53(a, b) = ((a >> 5) 2^26 + (b >> 6)) 2^-53 in [0, 1).
+ *   Real (either prior)  the column is u (the transformed space is the warped unit interval)
+ *   Integer, span s      0.0 when s == 0, else rint(u s) / s in fp64, ties to even: the
+ *                        grid k/s of Integer.transform, the end values with half the
+ *                        mass of the inner ones, as skopt's round of a uniform draw gives
+ *   Categorical, c       j = min((int)(u c), c - 1); one column: (double)j; else the
+ *                        one-hot row of j
+ * Against the host path the distribution differs on a set of measure zero only (the
+ * host draws Reals with an inclusive upper bound and round-trips them through
+ * inverse_transform / transform, a few ulp); the bits and the RandomState stream differ.
+ * dims is a HOST array; it reaches the kernel by value, so there is no workspace and no
+ * upload.  Every argument is validated before any GPU call.  m == 0 returns MPO_OK and
+ * launches nothing; first < 0, m < 0 and first + m > 2^62 return MPO_EINVAL, as do a
+ * null or misaligned (8 B) out with m > 0, an unknown kind and a count outside its
+ * range.  Only enqueues on `stream`: no allocation, no synchronisation, capturable. */
+int mpo_space_sample(const MpoDimDesc* dims, int n_dims, int d, uint64_t seed, int64_t first, int64_t m,
+                     double* out, void* stream);
+
+/* ------------------------------------------------------------------------
  * L-BFGS-B drivers (host C++, no Python in the loop).  skopt's refit runs
  * scipy.optimize.minimize(method="L-BFGS-B") from sklearn's
  * _constrained_optimization (_gpr.py:296-337) and its polish runs

@@ -22,6 +22,8 @@ ACQ_FLAGS = {"EI": MPO_ACQ_EI, "PI": MPO_ACQ_PI, "LCB": MPO_ACQ_LCB}
 LOSS_CODES = {"binary_crossentropy": 0x0, "categorical_crossentropy": 0x1}
 OPT_CODES = {"adam": 0x000, "sgd": 0x100}
 ACQ_ROW = {"EI": 0, "PI": 1, "LCB": 2}
+# MpoDimDesc.kind (include/mpo.h MPO_DIM_*)
+MPO_DIM_REAL, MPO_DIM_INTEGER, MPO_DIM_CATEGORICAL = 0, 1, 2
 
 
 class MpoError(RuntimeError):
@@ -36,6 +38,10 @@ class MpoGpModel(ctypes.Structure):
         ("wfrag", ctypes.c_void_p), ("L", ctypes.c_void_p), ("W", ctypes.c_void_p),
         ("info", ctypes.c_void_p), ("wmeta", ctypes.c_void_p), ("xb", ctypes.c_void_p),
     ]
+
+
+class MpoDimDesc(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int32), ("pad", ctypes.c_int32), ("count", ctypes.c_int64)]
 
 
 class MpoLbfgsbOptions(ctypes.Structure):
@@ -101,6 +107,7 @@ SIGNATURES = {
     "mpo_gp_ei_score": (_I, [ctypes.POINTER(MpoGpModel), _P, _I64, _D, _D, _P, _P, _P, _P, _P, _SZ, _P]),
     "mpo_gp_acq_grad": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _D, _D, _D, _P, _P, _P]),
     "mpo_gp_acq_grad_host": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _D, _D, _D, _P, _P, _P]),
+    "mpo_space_sample": (_I, [ctypes.POINTER(MpoDimDesc), _I, _I, ctypes.c_uint64, _I64, _I64, _P, _P]),
     "mpo_lbfgsb_batched": (_I, [_I, _I, _P, _P, ctypes.POINTER(MpoLbfgsbOptions), FG_BATCH_FN, _P, _P, _P, _P,
                                 _P]),
     "mpo_gp_lml_batcher_create": (_I, [_I, ctypes.POINTER(ctypes.c_void_p)]),

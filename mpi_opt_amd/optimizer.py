@@ -184,10 +184,23 @@ def _record_refit(n, t_refit, t_prepare, t_score, t_polish, t_propose, t_total, 
         STATS["samples"].append((n, t_total))      # (n, seconds of refit + proposal)
 
 
+def _gather_winners(X, index_lists):
+    """{candidate index: its row on the host} for the rows of the device tensor ``X`` that
+    won a top-k: one gather of the few winners (3 x n_restarts_optimizer at most)."""
+    import torch
+
+    idx = np.unique(np.concatenate([np.asarray(i, dtype=np.int64).ravel() for i in index_lists]))
+    rows = X[torch.from_numpy(idx).to(X.device)].cpu().numpy()
+    return dict(zip(idx.tolist(), rows))
+
+
 STRATEGIES = ("cl_min", "cl_mean", "cl_max")
 #: Optimizer(lie_refit=...): refit the hyper-parameters for every lie of an ask(n) batch
 #: (skopt) or for none of them
 LIE_REFIT = ("every", "never")
+#: Optimizer(candidates=...): where the acquisition candidates of a proposal are drawn
+#: (mpi_opt_amd.candidates): "host" is skopt's RandomState stream, "device" is not
+CANDIDATES = ("host", "device")
 
 #: the most observations one GP takes (the refit's and the scoring kernels' bound in libmpo.so)
 MAX_GP_POINTS = 2048
@@ -347,14 +360,29 @@ class Optimizer:
     ``ask(n)``, a hyper-parameter refit per constant-liar lie.  "never" departs from it:
     the lies of a batch keep the theta of the copy's newest model and extend its
     posterior by one observation each (``mpo_gp_append``, O(n^2)); a copy without a
-    model does one full fit first.  ``tell`` on the asking optimizer always refits."""
+    model does one full fit first.  ``tell`` on the asking optimizer always refits.
+
+    ``candidates`` ("host" | "device", an addition of this build): "host" is skopt's
+    candidate set, ``n_points`` rows drawn column by column from the optimizer's
+    RandomState and copied to the GPU.  "device" departs from it: a proposal draws ONE
+    seed from the RandomState and the rows are written on the GPU as a pure function of
+    (seed, row) (``mpo_space_sample``, :mod:`~mpi_opt_amd.candidates`).  Not skopt's
+    stream: other bits, other RandomState draws; the same distribution up to a set of
+    measure zero (Reals exclude the upper bound and skip the host's
+    inverse_transform / transform round trip of a few ulp)."""
 
     def __init__(self, dimensions, base_estimator="gp", n_random_starts=None, n_initial_points=10,
                  initial_point_generator="random", acq_func="gp_hedge", acq_optimizer="auto",
                  random_state=None, model_queue_size=None, acq_func_kwargs=None, acq_optimizer_kwargs=None,
-                 device=None, _gp_seed=None, scorer=None, chain_executor=None, lie_refit="every"):
+                 device=None, _gp_seed=None, scorer=None, chain_executor=None, lie_refit="every",
+                 candidates="host"):
         if lie_refit not in LIE_REFIT:
             raise ValueError(f"lie_refit {lie_refit!r}: one of {LIE_REFIT}")
+        if candidates not in CANDIDATES:
+            raise ValueError(f"candidates {candidates!r}: one of {CANDIDATES}")
+        # "host": skopt's candidate stream.  "device" (NOT the reference's stream): one seed
+        # draw per proposal, the candidates written on the GPU (mpo_space_sample).
+        self.candidates = candidates
         # "every": skopt's ask(n) -- a hyper-parameter refit per constant-liar lie.  "never"
         # (NOT the reference's semantics): the batch keeps the theta of the copy's model and
         # extends its posterior by one observation per lie (GPModel.appended).
@@ -407,6 +435,7 @@ class Optimizer:
         d.setdefault("trace", None)
         d.setdefault("chain_executor", None)
         d.setdefault("lie_refit", "every")
+        d.setdefault("candidates", "host")
         self.__dict__.update(d)
 
     def _config(self):
@@ -415,7 +444,7 @@ class Optimizer:
                     n_initial_points=self.n_initial_points_, initial_point_generator=self._initial_point_generator,
                     acq_func=self.acq_func, acq_optimizer=self.acq_optimizer, acq_func_kwargs=self.acq_func_kwargs,
                     acq_optimizer_kwargs=self.acq_optimizer_kwargs, _gp_seed=self._gp_seed,
-                    lie_refit=self.lie_refit)
+                    lie_refit=self.lie_refit, candidates=self.candidates)
 
     # ---- ask -------------------------------------------------------------------
     def copy(self, random_state=None):
@@ -515,7 +544,16 @@ class Optimizer:
             if self.model_queue_size is not None and len(self.models) > self.model_queue_size:
                 self.models.pop(0)
 
-        X = self.space.rvs_transformed(n_samples=self.n_points, random_state=self.rng)
+        cand_seed = None
+        if self.candidates == "device":
+            # one draw, so a batch stays a pure function of its ChainJob; the rows never
+            # exist on the host (X is a device tensor; only the winners are gathered below)
+            from .candidates import sample_transformed
+
+            cand_seed = int(self.rng.randint(0, np.iinfo(np.int32).max))
+            X = sample_transformed(self.space, self.n_points, cand_seed, device=self.device)
+        else:
+            X = self.space.rvs_transformed(n_samples=self.n_points, random_state=self.rng)
         y_opt = float(np.min(self.yi))
         xi = self.acq_func_kwargs.get("xi", 0.01)
         kappa = self.acq_func_kwargs.get("kappa", 1.96)
@@ -526,16 +564,24 @@ class Optimizer:
         t_polish = 0.0
         rec = {"theta": (est.amp, est.length_scale.copy(), est.noise), "top": dict(top), "polished": {}} \
             if self.trace is not None else None
+        if cand_seed is not None:
+            # X stays the device tensor; the host sees the winning rows only
+            won = _gather_winners(X, [top[a] for a in self.cand_acq_funcs_])
+            cand_row = lambda i: won[int(i)]  # noqa: E731
+            if rec is not None:
+                rec["cand_seed"] = cand_seed
+        else:
+            cand_row = lambda i: X[i]  # noqa: E731
         self.next_xs_ = []
         if self.acq_optimizer == "lbfgs":
             runs = [(a, i) for a in self.cand_acq_funcs_ for i in top[a]]
-            polished = polish_lockstep(est, [X[i] for _, i in runs], [a for a, _ in runs], y_opt, xi, kappa,
+            polished = polish_lockstep(est, [cand_row(i) for _, i in runs], [a for a, _ in runs], y_opt, xi, kappa,
                                        self.space.transformed_bounds, driver=DRIVER)
             t_polish = time.perf_counter() - t4
         for acq in self.cand_acq_funcs_:
             idx = top[acq]
             if self.acq_optimizer == "sampling":
-                next_x = X[idx[0]]
+                next_x = cand_row(idx[0])
             else:
                 results = [polished[w] for w, (a, _) in enumerate(runs) if a == acq]
                 cand_xs = np.array([r[0] for r in results])

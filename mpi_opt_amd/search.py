@@ -26,6 +26,11 @@ concern mpi_learn's file loader; the data here is resident in HBM.
 skopt refits the GP hyper-parameters for every constant-liar lie of an ask batch;
 ``never`` keeps the theta of the last told model for the whole batch and appends
 each lie to the posterior (``mpo_gp_append``).
+
+``--candidate-source device`` (an addition, default ``host``) departs from the
+reference too: the ``--ei-candidates`` acquisition candidates of a proposal are
+written on the GPU from one seed (``mpo_space_sample``, mpi_opt_amd.candidates)
+instead of being drawn from the optimizer's RandomState on the host.
 """
 from __future__ import annotations
 
@@ -85,7 +90,14 @@ def make_parser():
     p.add_argument("--history-dir", default=None, help="write per-trial history JSON here")
     p.add_argument("--checkpoint", default="coordinator.pkl")
     p.add_argument("--ei-candidates", type=int, default=10000,
-                   help="acquisition candidates per ask (skopt n_points); split over the GPUs when distributed")
+                   help="acquisition candidates per ask (skopt n_points); split over the GPUs when distributed, "
+                        "except with --candidate-source device, whose candidates are scored on the asking "
+                        "rank's GPU and never split")
+    p.add_argument("--candidate-source", default="host", choices=["host", "device"], dest="candidate_source",
+                   help="where the acquisition candidates of an ask are drawn: host (skopt's RandomState "
+                        "stream, copied to the GPU) or device (NOT the reference's stream: one seed per "
+                        "proposal, the candidates written on the GPU as a function of (seed, row); for "
+                        "large --ei-candidates; scored on the asking rank's GPU)")
     p.add_argument("--chain-workers", type=int, default=8,
                    help="concurrent cl_min ask batches per GPU (worker threads, one HIP stream each; their "
                         "refit rounds share launches); 0 runs every ask inline, as the reference's "
@@ -223,6 +235,8 @@ def run_search(args, x=None, y=None, log=print, progress=None, on_population=Non
     opt_kw = {"device": dev, "acq_optimizer_kwargs": {"n_points": args.ei_candidates}}
     if args.lie_refit != "every":
         opt_kw["lie_refit"] = args.lie_refit              # fixed-theta ask batches (not skopt's semantics)
+    if args.candidate_source != "host":
+        opt_kw["candidates"] = args.candidate_source      # device-drawn candidates (not skopt's stream)
     if chains is not None:
         opt_kw["chain_executor"] = chains                 # ask batches run concurrently (mpi_opt_amd.chains)
     if dist is not None:
