@@ -18,8 +18,7 @@
 //   1. K = amp * Matern52(|x_i/ls - x_j/ls|) + (noise + 1e-10) I   -> LDS, packed
 //      lower, column-major
 //   2. Cholesky in LDS, blocked by 8-column panels (update / diagonal block /
-//      rows below, three barriers per panel); the global variant is right-looking,
-//      one barrier per column
+//      rows below, three barriers per panel)
 //   3. the factor moves to the global workspace (row-major packed) and L^-1 is
 //      built in the LDS (row-major packed), blocked by 64 rows: diagonal blocks
 //      inverted in parallel, then block rows from the top
@@ -27,7 +26,9 @@
 //   5. per pair (i >= j): K^-1_ij = sum_m L^-1_mi L^-1_mj (LDS), W = a_i a_j - K^-1_ij,
 //      recompute dK_ij/dtheta and accumulate W dK (x2 off the diagonal)
 //   6. fixed-order reduction -> grad = 0.5 * sum_ij W_ij dK_ij/dtheta
-// For n > 200 the same code runs with the factor and L^-1 in the global workspace.
+// Every n past kSplitMinN (and so every n > 200) takes the block sweep below; the
+// variant of this kernel that kept the factor and L^-1 in the global workspace had
+// no caller left and is gone.
 // Everything is deterministic: fixed summation orders, no atomics.
 
 #include "mpo_internal.h"
@@ -64,8 +65,9 @@ struct LmlArgs {
 
 __host__ __device__ inline long long fit_tri(long long n) { return n * (n + 1) / 2; }
 
-// per-theta workspace (doubles): xs [n][d] | z [n] | alpha [n] | factor, packed [n(n+1)/2]
-// | L^-1 [n][n] (global variant only)
+// per-theta workspace (doubles): xs [n][d] | z [n] | alpha [n] | factor, packed [n(n+1)/2].
+// lds = false adds the [n][n] the removed global-memory variant used: only
+// mpo_gp_lml_ws_bytes still asks for it, so that the size it reports never shrinks.
 __host__ __device__ inline long long fit_ws_doubles(int n, int d, bool lds) {
     auto al = [](long long x) { return (x + 31) & ~31LL; };
     return al((long long)n * d) + 2 * al(n) + al(fit_tri(n)) + (lds ? 0 : al((long long)n * n));
@@ -86,7 +88,7 @@ __device__ __forceinline__ double readlane_f64(double v, int l) {
     return __longlong_as_double(((unsigned long long)hi << 32) | lo);
 }
 
-template <bool kLds, int DP>
+template <int DP>
 __global__ __launch_bounds__(kFitThreads) void lml_grad_kernel(LmlArgs a) {
     extern __shared__ __attribute__((aligned(16))) double fsm[];
     const int b = blockIdx.x;
@@ -100,11 +102,8 @@ __global__ __launch_bounds__(kFitThreads) void lml_grad_kernel(LmlArgs a) {
     double* z = xs + al((long long)n * d);
     double* alpha = z + al(n);
     double* Lg = alpha + al(n);              // global packed factor
-    double* Linv_g = Lg + al(fit_tri(n));    // global variant: L^-1 [n][n]
-    // LDS variant: the factor is built in LDS (column-major packed) and copied to Lg
-    // (row-major packed) before L^-1 takes the LDS over (row-major packed).
-    // Global variant: the factor lives in Lg column-major, L^-1 in Linv_g.
-    double* Lp = kLds ? fsm : Lg;
+    // The factor is built in LDS (column-major packed) and copied to Lg (row-major
+    // packed) before L^-1 takes the LDS over (row-major packed).
     auto cidx = [n](int i, int j) { return j * n - j * (j - 1) / 2 + (i - j); };
     auto ridx = [](int i, int j) { return i * (i + 1) / 2 + j; };
 
@@ -144,16 +143,16 @@ __global__ __launch_bounds__(kFitThreads) void lml_grad_kernel(LmlArgs a) {
                 const double k = sqrt(r2) * kSqrt5;
                 v = amp * ((1.0 + k + k * k / 3.0) * exp(-k));
             }
-            Lp[cidx(i, j)] = v;
+            fsm[cidx(i, j)] = v;
         }
     }
     __syncthreads();
     if (a.stop == 1) return;
 
     // ---- 2. Cholesky
-    double logdet = 0.0, prev_rs = 0.0;
+    double logdet = 0.0;
     int fail = 0;
-    if (kLds) {
+    {
         // Blocked by PW-column panels, three barriers per panel instead of one per column:
         //  (u) A[p0:, panel] -= L[p0:, :p0] L[panel, :p0]^T   (all waves; task = column j
         //      x 64-row chunk, lane = row: column-major reads are lane-contiguous)
@@ -251,49 +250,21 @@ __global__ __launch_bounds__(kFitThreads) void lml_grad_kernel(LmlArgs a) {
         fail = fm == 0x7fffffff ? 0 : fm;
         logdet = wave_sum_bcast(ld);
     }
-    for (int j = 0; j < (kLds ? 0 : n); ++j) {
-        const double dj = Lp[cidx(j, j)];
-        if (!(dj > 0.0) || !isfinite(dj)) { fail = j + 1; break; }  // uniform: every thread reads dj
-        const double rs = sqrt(dj);
-        logdet += log(rs);
-        const double inv = 1.0 / dj;
-        if (j > 0) {  // finalise column j-1 (not read by this step's update)
-            const int c0 = cidx(j - 1, j - 1);
-            for (int e = tid; e < n - j + 1; e += kFitThreads) Lp[c0 + e] = e == 0 ? prev_rs : Lp[c0 + e] / prev_rs;
-        }
-        const int cj = cidx(j, j);
-        for (int k = j + 1 + wave; k < n; k += kFitWaves) {
-            const double lkj = Lp[cj + (k - j)] * inv;
-            const int ck = cidx(k, k);
-            for (int i = k + lane; i < n; i += 64) Lp[ck + (i - k)] -= Lp[cj + (i - j)] * lkj;
-        }
-        prev_rs = rs;
-        __syncthreads();
-    }
     if (fail) {  // sklearn: LinAlgError -> (-inf, zeros)
         if (tid == 0) { a.lml[b] = -INFINITY; a.info[b] = fail; }
         for (int c = tid; c < d + 2; c += kFitThreads) a.grad[(long long)b * (d + 2) + c] = 0.0;
         return;
     }
-    if (!kLds && tid == 0) Lp[cidx(n - 1, n - 1)] = prev_rs;
     __syncthreads();
     if (a.stop == 2) return;
 
-    // ---- 3. L^-1 by columns: thread c forward-substitutes e_c.  Row i of L is read
-    // wave-uniformly (scalar loads); the solution column is the thread's own
-    // (LDS in the LDS variant).  Entries above the diagonal are never stored or read.
-    if (kLds) {
-        for (int i = wave; i < n; i += kFitWaves)
-            for (int j = lane; j <= i; j += 64) Lg[ridx(i, j)] = fsm[cidx(i, j)];
-        __syncthreads();
-    }
-    auto lrow = [&](int i, int k) -> double { return kLds ? Lg[ridx(i, k)] : Lg[cidx(i, k)]; };
-    auto lv = [&](int m, int j) -> double { return kLds ? fsm[ridx(m, j)] : Linv_g[m * n + j]; };
-    auto lv_set = [&](int m, int j, double v) {
-        if (kLds) fsm[ridx(m, j)] = v;
-        else Linv_g[m * n + j] = v;
-    };
-    if (kLds) {
+    // ---- 3. L^-1 in the LDS (row-major packed); entries above the diagonal are never
+    // stored or read
+    for (int i = wave; i < n; i += kFitWaves)
+        for (int j = lane; j <= i; j += 64) Lg[ridx(i, j)] = fsm[cidx(i, j)];
+    __syncthreads();
+    auto lv = [&](int m, int j) -> double { return fsm[ridx(m, j)]; };
+    {
         // Blocked in 64-row blocks (n <= 200: at most 4), the dtrtri scheme:
         //  3a. every diagonal block is inverted at once, one wave per block, thread c
         //      forward-substituting e_c inside its block (chains of <= 64 rows
@@ -395,18 +366,6 @@ __global__ __launch_bounds__(kFitThreads) void lml_grad_kernel(LmlArgs a) {
             }
             __syncthreads();
         }
-    } else {
-        for (int c0 = wave * 64; c0 < n; c0 += kFitThreads) {
-            const int c = c0 + lane;
-            const int cr = c < n ? c : n - 1;
-            for (int i = c0; i < n; ++i) {
-                double s0 = 0.0;
-                for (int k = c0; k < i; ++k) s0 += k >= cr ? lrow(i, k) * lv(k, cr) : 0.0;
-                const double lii = lrow(i, i);
-                const double x = i == cr ? 1.0 / lii : -s0 / lii;
-                if (c < n && i >= c) lv_set(i, c, x);
-            }
-        }
     }
     __syncthreads();
     if (a.stop == 3) return;
@@ -438,7 +397,7 @@ __global__ __launch_bounds__(kFitThreads) void lml_grad_kernel(LmlArgs a) {
         for (int j = lane; j <= i; j += 64) {
             double k0 = 0.0, k1 = 0.0;
             int m = i;
-            if (kLds) {
+            {
                 int r = ridx(i, 0);  // start of row m (packed row-major), advanced by m + 1
                 // batches of 8 rows: all 16 LDS loads issued before the FMAs
                 for (; m + 7 < n; m += 8) {
@@ -459,8 +418,6 @@ __global__ __launch_bounds__(kFitThreads) void lml_grad_kernel(LmlArgs a) {
                     k0 += fsm[r + i] * fsm[r + j];
                     r += m + 1;
                 }
-            } else {
-                for (; m < n; ++m) k0 += lv(m, i) * lv(m, j);
             }
             const double kinv = k0 + k1;
             const double W = (ai * alpha[j] - kinv) * (i == j ? 1.0 : 2.0);
@@ -1646,10 +1603,13 @@ inline bool fit_fused_split(int n, int dp) {
     return use_split(n) && (size_t)sw_np(n) * dp * sizeof(double) <= 64 * 1024;
 }
 
-template <bool kLds, int DP>
+template <int DP>
 int launch_lml(const LmlArgs& a, int B, hipStream_t s) {
-    auto kern = lml_grad_kernel<kLds, DP>;
-    const size_t lds = kLds ? (size_t)fit_tri(a.n) * sizeof(double) : (size_t)kFitWaves * (DP + 2) * sizeof(double);
+    auto kern = lml_grad_kernel<DP>;
+    // the packed factor, and no less than phase 6's [kFitWaves][DP + 2] reduction, which
+    // reuses it: the triangle alone is the smaller one up to n = 13 / 17 / 20 / 23 / 32 at
+    // DP = 4 / 8 / 12 / 16 / 32, and waves' partial sums then lay past the allocation
+    const size_t lds = std::max((size_t)fit_tri(a.n), (size_t)kFitWaves * (DP + 2)) * sizeof(double);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kern, dim3(B), dim3(kFitThreads), lds, s, a);
     MPO_LAUNCH_CHECK();
@@ -1711,10 +1671,9 @@ static int lml_grad_impl(const double* X, const double* y_norm, int n, int d, co
     }
     MPO_CHECK_ARG(ws_bytes >= mpo_gp_lml_ws_bytes(n, d, batch), "mpo_gp_lml_grad: workspace too small (%zu < %zu)",
                   ws_bytes, mpo_gp_lml_ws_bytes(n, d, batch));
-    const bool use_lds = n <= kFitLdsMaxN;
     const bool split = use_split(n);
     double* wsa = reinterpret_cast<double*>(mpo::align_up(reinterpret_cast<uintptr_t>(ws), 256));
-    LmlArgs a{X, y_norm, n, d, theta, lml, grad, info, wsa, fit_ws_doubles(n, d, use_lds), 0};
+    LmlArgs a{X, y_norm, n, d, theta, lml, grad, info, wsa, fit_ws_doubles(n, d, true), 0};
     int stop = 0;
     if (const char* e = getenv("MPO_FIT_DEBUG")) stop = a.stop = atoi(e);
     a.theta_src = split && fit_fused_split(n, dp) ? theta_src : nullptr;
@@ -1726,21 +1685,15 @@ static int lml_grad_impl(const double* X, const double* y_norm, int n, int d, co
         problem_thetas(th, X, y_norm, n, d, dp, theta, a.theta_src, batch, lml, grad, info, wsa);
         return launch_split_any(th, d, stop, s);
     }
-    if (use_lds) {
-        switch (dp) {
-            case 4: return launch_lml<true, 4>(a, batch, s);
-            case 8: return launch_lml<true, 8>(a, batch, s);
-            case 12: return launch_lml<true, 12>(a, batch, s);
-            case 16: return launch_lml<true, 16>(a, batch, s);
-            default: return launch_lml<true, 32>(a, batch, s);
-        }
-    }
+    // use_split sends every n > kSplitMinN to the sweep unless MPO_FIT_KERNEL=panel holds
+    // it back, which it does only for n <= kFitLdsMaxN: the factor always fits the LDS here
+    MPO_CHECK_ARG(n <= kFitLdsMaxN, "mpo_gp_lml_grad: n=%d past the Cholesky kernel's LDS limit %d", n, kFitLdsMaxN);
     switch (dp) {
-        case 4: return launch_lml<false, 4>(a, batch, s);
-        case 8: return launch_lml<false, 8>(a, batch, s);
-        case 12: return launch_lml<false, 12>(a, batch, s);
-        case 16: return launch_lml<false, 16>(a, batch, s);
-        default: return launch_lml<false, 32>(a, batch, s);
+        case 4: return launch_lml<4>(a, batch, s);
+        case 8: return launch_lml<8>(a, batch, s);
+        case 12: return launch_lml<12>(a, batch, s);
+        case 16: return launch_lml<16>(a, batch, s);
+        default: return launch_lml<32>(a, batch, s);
     }
     MPO_GUARD_END
 }
