@@ -353,7 +353,11 @@ int mpo_gp_polish_host(const MpoGpModel* model, const double* starts, const int3
  * ---------------------------------------------------------------------- */
 
 /* One population member: the test_mnist hyper-parameters (option3:127-131)
- * plus the optimizer/dropout settings that the device table carries per trial. */
+ * plus the optimizer/dropout settings that the device table carries per trial.
+ * Accepted (each extreme is compared with the fp64 oracle, tests/pop_cases.py):
+ * nb_filters 1..64, kernel_size 1..10, pool_size 1..16 with pool_size <= 30 - 2 k
+ * (one pool window at least), dense 1..4096, 0 <= dropout < 1, lr > 0.  The
+ * comments below give option3's search space, which lies inside. */
 typedef struct MpoCnnSpec {
     int32_t nb_filters;   /* F      Integer(10, 50)  */
     int32_t kernel_size;  /* k      Integer(2, 10)   */
@@ -383,7 +387,11 @@ typedef struct MpoPopSizes {
 } MpoPopSizes;
 
 /* Plan a population (host only: layouts, ragged work lists).  *handle owns host
- * memory only; release with mpo_pop_destroy. */
+ * memory only; release with mpo_pop_destroy.  n_members >= 1, batch 1..256 (else
+ * MPO_EINVAL); a member outside MpoCnnSpec's accepted ranges returns MPO_ENOTSUP with
+ * the member and the reason in mpo_last_error(): kernel_size > 10 (the conv1 weight
+ * gradient holds k*k + 1 <= 112 rows per wave) and pool_size > 16 (the max-pool argmax
+ * is one byte) computed wrong gradients before they were refused. */
 int mpo_pop_create(const MpoCnnSpec* specs, int n_members, int batch, void** handle);
 int mpo_pop_destroy(void* handle);
 int mpo_pop_sizes(const void* handle, MpoPopSizes* out);

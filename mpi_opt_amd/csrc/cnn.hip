@@ -1130,7 +1130,7 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(StepArgs a, const MItem* 
     float* dz2 = a.act + mb.dz2 + (long long)b * H2 * H2 * F;
     const int n = H2 * H2 * F;
     // division-free walk over (y, x, f): each thread advances by blockDim.x elements
-    const float inv_p = 1.f / (float)p;   // floor((x + 0.5) / p) is exact for x < 64, p <= 13
+    const float inv_p = 1.f / (float)p;   // floor((x + 0.5) / p) is exact for x < 64, p <= 16
     const int step = blockDim.x, df = step % F, dq = step / F;
     int f = threadIdx.x % F, q = threadIdx.x / F;
     int x = q % H2, y = q / H2;
@@ -1834,7 +1834,22 @@ int build_plan(Plan& P, const MpoCnnSpec* specs, int n, int B) {
     for (int i = 0; i < n; ++i) {
         const MpoCnnSpec& s = specs[i];
         Member& m = P.mem[i];
-        if (s.nb_filters < 1 || s.nb_filters > 64 || s.kernel_size < 1 || s.kernel_size > 13 || s.pool_size < 1 ||
+        // The accepted domain is what tests/pop_cases.py compares with the oracle at its
+        // extremes: F 1..64, k 1..10, p 1..16, dense 1..4096 (batch 1..256).
+        if (s.kernel_size > 10) {
+            // conv1_wgrad_kernel holds at most 7 m-tiles (112 rows) per wave: k*k + 1 = 122 rows
+            // at k = 11 left the w1 rows past 112 and the b1 row unwritten (zero gradients)
+            mpo::set_error("mpo_pop_create: member %d has kernel_size %d > 10: the conv1 weight gradient holds at most "
+                           "7 m-tiles of 16 rows (k*k + 1 <= 112)", i, s.kernel_size);
+            return MPO_ENOTSUP;
+        }
+        if (s.pool_size > 16) {
+            // pool_fwd_kernel stores the argmax dy * p + dx in one byte: it wraps from p = 17 on
+            mpo::set_error("mpo_pop_create: member %d has pool_size %d > 16: the max-pool argmax dy * p + dx is stored "
+                           "in one byte", i, s.pool_size);
+            return MPO_ENOTSUP;
+        }
+        if (s.nb_filters < 1 || s.nb_filters > 64 || s.kernel_size < 1 || s.pool_size < 1 ||
             s.dense < 1 || s.dense > 4096 || !(s.dropout >= 0.f && s.dropout < 1.f) || !(s.lr > 0.f)) {
             mpo::set_error("mpo_pop_create: member %d has unsupported spec (F=%d k=%d p=%d dense=%d lr=%g dropout=%g)", i,
                            s.nb_filters, s.kernel_size, s.pool_size, s.dense, s.lr, s.dropout);
