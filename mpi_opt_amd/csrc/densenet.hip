@@ -453,7 +453,8 @@ __global__ __launch_bounds__(256) void dn_conv_kernel(ConvArgs a) {
         // the consumer's dn_bn_bwd_reduce on the values just produced (dz = this output):
         // dy = dz ELU'(x scale + shift), sums of dy and dy xhat per image row -- a lane's
         // four pixels share a row (W % 4 == 0); a 16-pixel tile is one row segment for
-        // W >= 16, 16 / W whole rows below; one (b, segment, row) slot per tile and row
+        // W >= 16 (W % 16 == 0: build_plan's bn_fS rule), 16 / W whole rows below; one
+        // (b, segment, row) slot per tile and row
         const float* xr = a.rx + m * a.rx_ms + ((long long)b * H + y0) * W * a.rx_ps;
         const float* cf = a.rcoef + m * a.rcoef_ms;
         const int SL = W >= 16 ? W / 16 : 1;
@@ -1719,11 +1720,16 @@ int build_plan(DnPlan& p) {
         bnp_max = std::max(bnp_max, (long long)p.bn_S[i] * ly.H * 2);
     }
     // the dense layers' BN backward reduce in their input-gradient conv's epilogue: one
-    // partial per (sample, 16-pixel row segment) slice
+    // partial per (sample, 16-pixel row segment) slice.  Only where an m-tile never
+    // straddles two rows: W a multiple of 16, or a divisor of 16 (at W = 24 the tile at
+    // pixel 16 would hold x = 16..23 of one row and x = 0..7 of the next); the other
+    // widths run dn_bn_bwd_reduce
     p.bn_fS.assign(ls.size(), 0);
     for (size_t i = 0; i < ls.size(); ++i) {
         const Layer& ly = ls[i];
-        if (!p.bnfuse || ly.kind != K_DENSE || ly.ks != 3 || ly.W % 4 != 0 || (ly.W < 16 && 16 % ly.W != 0)) continue;
+        if (!p.bnfuse || ly.kind != K_DENSE || ly.ks != 3 || ly.W % 4 != 0 ||
+            (ly.W >= 16 ? ly.W % 16 != 0 : 16 % ly.W != 0))
+            continue;
         p.bn_fS[i] = B * std::max(1, ly.W / 16);
         bnp_max = std::max(bnp_max, (long long)p.bn_fS[i] * ly.H * 2);
     }
