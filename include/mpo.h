@@ -230,6 +230,15 @@ int mpo_gp_ei_score(const MpoGpModel* model, const double* cand, int64_t m,
 int mpo_gp_acq_grad(const MpoGpModel* model, const double* x, int batch, const int32_t* acq,
                     double y_opt, double xi, double kappa, double* f, double* g, void* stream);
 
+/* Which form of the polish kernel mpo_gp_acq_grad launches for this model: 16 waves per
+ * point while 19 n doubles plus the kernel's static LDS fit the 160 KiB LDS (n <= 914),
+ * 4 waves per point (7 n doubles) past it; negative (-MPO_EINVAL: null or unprepared
+ * model, -MPO_ENOTSUP: n too large for either) when mpo_gp_acq_grad would refuse the
+ * model.  The launch makes its choice through the same helper.  Reads only model->n once
+ * the model is accepted; needs a device, because the static LDS size is asked of the code
+ * object (without one every model is answered -MPO_ENOTSUP). */
+int mpo_gp_acq_grad_path(const MpoGpModel* model);
+
 /* One polish round from the host: mpo_gp_acq_grad with x, acq, f, g in pinned
  * (hipHostMalloc / registered) host memory, read and written by the kernel in
  * place (no staging copies), then a synchronisation of `stream`.  MPO_EINVAL if

@@ -106,6 +106,7 @@ SIGNATURES = {
                               _P, _SZ, _P]),
     "mpo_gp_ei_score": (_I, [ctypes.POINTER(MpoGpModel), _P, _I64, _D, _D, _P, _P, _P, _P, _P, _SZ, _P]),
     "mpo_gp_acq_grad": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _D, _D, _D, _P, _P, _P]),
+    "mpo_gp_acq_grad_path": (_I, [ctypes.POINTER(MpoGpModel)]),
     "mpo_gp_acq_grad_host": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _D, _D, _D, _P, _P, _P]),
     "mpo_space_sample": (_I, [ctypes.POINTER(MpoDimDesc), _I, _I, ctypes.c_uint64, _I64, _I64, _P, _P]),
     "mpo_lbfgsb_batched": (_I, [_I, _I, _P, _P, ctypes.POINTER(MpoLbfgsbOptions), FG_BATCH_FN, _P, _P, _P, _P,

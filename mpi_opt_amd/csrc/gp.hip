@@ -2190,20 +2190,46 @@ int mpo_gp_ei_score(const MpoGpModel* model, const double* cand, int64_t m, doub
     MPO_GUARD_END
 }
 
-int mpo_gp_acq_grad(const MpoGpModel* model, const double* x, int batch, const int32_t* acq, double y_opt,
-                    double xi, double kappa, double* f, double* g, void* stream) {
-    MPO_GUARD_BEGIN
-    MPO_CHECK_ARG(model && x && acq && f && g, "mpo_gp_acq_grad: null pointer");
-    MPO_CHECK_ARG(batch > 0 && batch <= 65535, "mpo_gp_acq_grad: batch=%d outside [1, 65535]", batch);
-    MPO_CHECK_ARG(model->n > 0 && model->d > 0 && model->d <= 32 && model->W, "mpo_gp_acq_grad: model not prepared");
+// The form mpo_gp_acq_grad launches for this model: *waves = 16 or 4 waves per point and
+// *lds its dynamic LDS bytes.  `who` (may be NULL: no message) names the entry point in
+// a refusal.  The one place the choice is made: the launch and mpo_gp_acq_grad_path
+// both ask here.
+static int acq_grad_plan(const char* who, const MpoGpModel* model, int* waves, size_t* lds) {
+    if (!(model && model->n > 0 && model->d > 0 && model->d <= 32 && model->W)) {
+        if (who) mpo::set_error("%s: model not prepared", who);
+        return MPO_EINVAL;
+    }
     // dynamic LDS per point: 19 n doubles (16 waves) or 7 n (4 waves); the static
     // part (reduction rows, gradient tiles) is read from each kernel's code object
     static const size_t st16 = mpo::static_lds_bytes(reinterpret_cast<const void*>(acq_grad_kernel<16>));
     static const size_t st4 = mpo::static_lds_bytes(reinterpret_cast<const void*>(acq_grad_kernel<4>));
     const size_t lds16 = (size_t)19 * model->n * sizeof(double), lds4 = (size_t)7 * model->n * sizeof(double);
     const bool wide = lds16 + st16 <= kMaxLds;
-    const size_t lds = wide ? lds16 : lds4;
-    if (!wide && lds4 + st4 > kMaxLds) { mpo::set_error("mpo_gp_acq_grad: n=%d too large", model->n); return MPO_ENOTSUP; }
+    if (!wide && lds4 + st4 > kMaxLds) {
+        if (who) mpo::set_error("%s: n=%d too large", who, model->n);
+        return MPO_ENOTSUP;
+    }
+    *waves = wide ? 16 : 4;
+    *lds = wide ? lds16 : lds4;
+    return MPO_OK;
+}
+
+int mpo_gp_acq_grad_path(const MpoGpModel* model) {
+    int waves = 0;
+    size_t lds = 0;
+    const int rc = acq_grad_plan(nullptr, model, &waves, &lds);
+    return rc ? -rc : waves;
+}
+
+int mpo_gp_acq_grad(const MpoGpModel* model, const double* x, int batch, const int32_t* acq, double y_opt,
+                    double xi, double kappa, double* f, double* g, void* stream) {
+    MPO_GUARD_BEGIN
+    MPO_CHECK_ARG(model && x && acq && f && g, "mpo_gp_acq_grad: null pointer");
+    MPO_CHECK_ARG(batch > 0 && batch <= 65535, "mpo_gp_acq_grad: batch=%d outside [1, 65535]", batch);
+    int waves = 0;
+    size_t lds = 0;
+    if (const int rc = acq_grad_plan("mpo_gp_acq_grad", model, &waves, &lds)) return rc;
+    const bool wide = waves == 16;
     auto kern = wide ? acq_grad_kernel<16> : acq_grad_kernel<4>;
     MPO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(batch), dim3(wide ? 1024 : 256), lds, static_cast<hipStream_t>(stream),

@@ -253,6 +253,14 @@ class DeviceGP:
             self._ag_stream = _lib.stream_handle(self.device)
             self._ag_cap = cap
 
+    @property
+    def acq_grad_path(self):
+        """``mpo_gp_acq_grad_path``: the waves per point (16 or 4) of the polish kernel
+        that ``acq_grad`` / ``polish`` launch for this model, negative when the model
+        would be refused.  Needs the device (the kernel's static LDS is read from it)."""
+        with torch.cuda.device(self.device):
+            return int(lib().mpo_gp_acq_grad_path(ctypes.byref(self.model)))
+
     def acq_grad(self, X, acq_codes, y_opt, xi=0.01, kappa=1.96):
         """``mpo_gp_acq_grad_host``: minimised acquisition value and gradient at
         the rows of X (B, d) (transformed space), acquisition ``acq_codes[b]``

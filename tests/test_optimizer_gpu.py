@@ -85,8 +85,11 @@ def test_acq_grad_matches_oracle(n, d):
     """mpo_gp_acq_grad (the polish objective) against the oracle's restatement of
     skopt gaussian_acquisition_1D: values and gradients of -EI, -PI and LCB at
     random points, at an observation (sd -> 0) and at the box corners.  n = 915 /
-    920 straddle the switch from the 16-wave to the 4-wave kernel (its LDS budget,
-    ADVICE r03), n = 1100 runs the 4-wave form well past it."""
+    920 are the first sizes past the switch from the 16-wave to the 4-wave kernel
+    (its LDS budget, ADVICE r03: 16 waves up to n = 914, as mpo_gp_acq_grad_path
+    reports), n = 1100 runs the 4-wave form well past it; the 16-wave form runs at
+    n <= 500 here and at n = 914 in test_gp_factor_shapes_gpu.py, which holds both
+    sides of the switch to the 1e-9 bars against an 80-bit or triangular reference."""
     from mpi_opt_amd.gp import DeviceGP
     from mpi_opt_amd import _lib
 
