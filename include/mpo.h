@@ -247,6 +247,60 @@ int mpo_gp_acq_grad_host(const MpoGpModel* model, const double* x_host, int batc
                          double y_opt, double xi, double kappa, double* f_host, double* g_host, void* stream);
 
 /* ------------------------------------------------------------------------
+ * The JOINT posterior of a prepared model over m query points (transformed space,
+ * [m][d] device): what sklearn's GaussianProcessRegressor.predict(X, return_cov=True)
+ * and sample_y(X, n_samples) give (_gpr.py:370-470, 472-507), for skopt's fitted GP
+ * (result.models[-1]).  Reads the model's plain W = L^-1, xs and alpha only: any
+ * prepared, appended or copied (from its exported workspace) model of n <= 2048
+ * observations is served, whatever its scoring path.  fp64 MFMA throughout; every sum
+ * runs in a fixed order, so two calls give the same bits.
+ * ---------------------------------------------------------------------- */
+#define MPO_JOINT_MAX 4096
+
+/* Workspace bytes of mpo_gp_posterior_cov (s = 0) or mpo_gp_sample (s >= 1 draws) over m
+ * query points: V = K* W^T [m32][np16], and for s >= 1 the [m32][m32] matrix that is
+ * factored (m32 = m rounded up to 32; 194 MiB at n = 2048, m = 4096).  0 if unsupported:
+ * null or malformed model, n > 2048, m < 1, m > MPO_JOINT_MAX, s < 0. */
+size_t mpo_gp_joint_ws_bytes(const MpoGpModel* model, int m, int s);
+
+/* mu [m] (or NULL: not written) and cov [m][ldc]:
+ *   mu = y_mean + y_std K* alpha,   cov = y_std^2 (amp Matern52(|c_i - c_j|) - V V^T),
+ * V = K* W^T, K* = amp Matern52(|c - xs|) by direct differences.  No noise term (skopt
+ * zeroes the WhiteKernel after the fit): diag(cov) is the sd^2 of mpo_gp_acq_score.
+ * cov is exactly symmetric (each lower 16 x 16 tile is written with its mirror).
+ * MPO_ENOTSUP: m > MPO_JOINT_MAX or n > 2048.  MPO_EINVAL: a null pointer (mu excepted),
+ * m < 1, ldc < m, a malformed model, a workspace smaller than
+ * mpo_gp_joint_ws_bytes(model, m, 0).  All checks run on the host before any launch.
+ * Only enqueues work: no allocation, no host synchronisation, capturable in a graph. */
+int mpo_gp_posterior_cov(const MpoGpModel* model, const double* cand, int m,
+                         double* mu /*[m] or NULL*/, double* cov /*[m][ldc]*/, int ldc,
+                         void* ws, size_t ws_bytes, void* stream);
+
+/* s correlated draws of the posterior at the m query points, and the argmin of each:
+ *   Lc Lc^T = Sigma_n + jitter amp I   (Sigma_n = cov / y_std^2; blocked Cholesky, the
+ *                                       kernels and step order of mpo_gp_prepare)
+ *   samples[r][i] = mu[i] + y_std sum_{j <= i} Lc[i][j] z[j][r]
+ *   argmin[r]     = the lowest index among the smallest samples[r][.]  (np.argmin)
+ * z [m][s] (device) holds the caller's standard normal variates; samples [s][m] and
+ * argmin [s] may each be NULL (not written).  *info (device int32): 0, or the first
+ * failed column + 1 as mpo_chol_f64 reports it -- the outputs are then meaningless and
+ * the caller retries with a larger jitter.
+ * MPO_ENOTSUP: m > MPO_JOINT_MAX or n > 2048.  MPO_EINVAL: a null model, cand, z, info or
+ * workspace, m < 1, s < 1, a negative or non-finite jitter, a malformed model, a
+ * workspace smaller than mpo_gp_joint_ws_bytes(model, m, s).  All checks run on the host
+ * before any launch.  Only enqueues work: no allocation, no host synchronisation.
+ * sklearn's sample_y draws through multivariate_normal's SVD: the same distribution,
+ * other bits.
+ * NOT the reference's semantics: skopt's ask(n_points) (Coordinator.ask,
+ * coordinator.py:46-50) is a constant-liar batch; this entry point serves the opt-in
+ * Thompson batch (Optimizer(batch_strategy="thompson") / ask(n, strategy="thompson")),
+ * and GPModel.sample_y. */
+int mpo_gp_sample(const MpoGpModel* model, const double* cand, int m,
+                  const double* z /*[m][s]*/, int s, double jitter /* >= 0, relative to amp */,
+                  double* samples /*[s][m] or NULL*/, int64_t* argmin /*[s] or NULL*/,
+                  int32_t* info, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Acquisition candidates drawn on the device (opt-in: Optimizer(candidates="device")).
  * skopt draws the n_points candidates of every ask on the host, column by column from
  * one RandomState (Space.rvs + transform, reached from Coordinator.ask,

@@ -17,6 +17,7 @@ MPO_ACQ_EI = 1
 MPO_ACQ_PI = 2
 MPO_ACQ_LCB = 4
 MPO_TOPK_MAX = 8
+MPO_JOINT_MAX = 4096
 ACQ_FLAGS = {"EI": MPO_ACQ_EI, "PI": MPO_ACQ_PI, "LCB": MPO_ACQ_LCB}
 # MpoCnnSpec.options: option3's --loss / --optimizer (include/mpo.h MPO_LOSS_* | MPO_OPT_*)
 LOSS_CODES = {"binary_crossentropy": 0x0, "categorical_crossentropy": 0x1}
@@ -108,6 +109,9 @@ SIGNATURES = {
     "mpo_gp_acq_grad": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _D, _D, _D, _P, _P, _P]),
     "mpo_gp_acq_grad_path": (_I, [ctypes.POINTER(MpoGpModel)]),
     "mpo_gp_acq_grad_host": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _D, _D, _D, _P, _P, _P]),
+    "mpo_gp_joint_ws_bytes": (_SZ, [ctypes.POINTER(MpoGpModel), _I, _I]),
+    "mpo_gp_posterior_cov": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _P, _I, _P, _SZ, _P]),
+    "mpo_gp_sample": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _I, _D, _P, _P, _P, _P, _SZ, _P]),
     "mpo_space_sample": (_I, [ctypes.POINTER(MpoDimDesc), _I, _I, ctypes.c_uint64, _I64, _I64, _P, _P]),
     "mpo_lbfgsb_batched": (_I, [_I, _I, _P, _P, ctypes.POINTER(MpoLbfgsbOptions), FG_BATCH_FN, _P, _P, _P, _P,
                                 _P]),

@@ -39,19 +39,12 @@ namespace {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
-constexpr double kSqrt5 = 2.236067977499789696409173668731276235;
+using mpo::kSqrt5;
+using mpo::matern52;   // mpo_internal.h: shared with gp_joint.hip
 constexpr double kSqrt1_2 = 0.707106781186547524400844362104849039;
 constexpr double kSqrt2Pi = 2.506628274631000502415765284811045253;
 constexpr double kJitter = 1e-10;
   // sklearn GPR alpha default (_gpr.py:207)
-
-// sklearn kernels.py:1715-1724 (nu = 2.5) times ConstantKernel.
-__device__ __forceinline__ double matern52(double r, double amp) {
-    // k^2 / 3 as a multiply by the rounded 1/3: within 1 ulp of sklearn's division,
-    // and an fp64 divide costs ~10 VALU ops per candidate-observation pair
-    const double k = r * kSqrt5;
-    return amp * ((1.0 + k + k * k * (1.0 / 3.0)) * exp(-k));
-}
 
 // exp(-k) for k >= 0 without the generic exp's special-case handling (k is a
 // scaled distance: never negative, never NaN): Cody-Waite reduction
@@ -1398,7 +1391,7 @@ __global__ __launch_bounds__(64) void bc_diag_kernel(double* __restrict__ A, int
         for (int j = 0; j < kBc; ++j) {
             if (j <= l) Akk[(size_t)l * np + j] = r[j];
             Dinv[(size_t)k * kBc * kBc + l * kBc + j] = j <= l ? p[j] : 0.0;
-            Wp[(size_t)(k0 + l) * np + k0 + j] = j <= l ? p[j] : 0.0;
+            if (Wp) Wp[(size_t)(k0 + l) * np + k0 + j] = j <= l ? p[j] : 0.0;
         }
     }
     if (lane == 0 && bad && info[0] == 0) info[0] = k0 + bad;
@@ -1530,14 +1523,11 @@ __global__ void bc_copy_out_kernel(const double* __restrict__ A, const double* _
     W[(size_t)i * n + j] = j <= i ? Wp[(size_t)i * np + j] : 0.0;
 }
 
-// The launch sequence of the blocked factorisation (+ alpha) on stream s.
-hipError_t blocked_factor(const double* xs, int n, int dp, double amp, double diag_add, const double* y_norm,
-                          double* A, double* Wp, double* Dinv, double* v, double* L, double* W, double* alpha,
-                          int32_t* info, hipStream_t s) {
-    const int np = bc_np(n), nbk = np / kBc;
-    (void)hipMemsetAsync(info, 0, sizeof(int32_t), s);
-    (void)hipMemsetAsync(Wp, 0, (size_t)np * np * sizeof(double), s);
-    hipLaunchKernelGGL(bc_kmat_kernel, dim3((np + 63) / 64, np), dim3(64), 0, s, xs, n, dp, amp, diag_add, A, np);
+// The block steps of A = L L^T in place on the padded np x np matrix (np a multiple of 32;
+// info zeroed by the caller).  Wp: the padded L^-1 whose diagonal blocks receive D_k, or
+// nullptr when only the factor is wanted (mpo::blocked_chol).
+void factor_blocks(double* A, int np, double* Dinv, double* Wp, int32_t* info, hipStream_t s) {
+    const int nbk = np / kBc;
     for (int k = 0; k < nbk; ++k) {
         hipLaunchKernelGGL(bc_diag_kernel, dim3(1), dim3(64), 0, s, A, np, k, Dinv, Wp, info);
         const int below = np / 16 - (k + 1) * 2;
@@ -1547,6 +1537,17 @@ hipError_t blocked_factor(const double* xs, int n, int dp, double amp, double di
         hipLaunchKernelGGL(bc_update_kernel, dim3(std::max(1, std::min(1024, (ntl + 3) / 4))), dim3(256), 0, s,
                            A, np, k);
     }
+}
+
+// The launch sequence of the blocked factorisation (+ alpha) on stream s.
+hipError_t blocked_factor(const double* xs, int n, int dp, double amp, double diag_add, const double* y_norm,
+                          double* A, double* Wp, double* Dinv, double* v, double* L, double* W, double* alpha,
+                          int32_t* info, hipStream_t s) {
+    const int np = bc_np(n), nbk = np / kBc;
+    (void)hipMemsetAsync(info, 0, sizeof(int32_t), s);
+    (void)hipMemsetAsync(Wp, 0, (size_t)np * np * sizeof(double), s);
+    hipLaunchKernelGGL(bc_kmat_kernel, dim3((np + 63) / 64, np), dim3(64), 0, s, xs, n, dp, amp, diag_add, A, np);
+    factor_blocks(A, np, Dinv, Wp, info, s);
     for (int I = 1; I < nbk; ++I)
         hipLaunchKernelGGL(bc_winv_kernel, dim3(I), dim3(256), 0, s, A, Wp, np, I, Dinv);
     hipLaunchKernelGGL(bc_wy_kernel, dim3((np + 3) / 4), dim3(256), 0, s, Wp, np, n, y_norm, v);
@@ -1963,6 +1964,14 @@ int finish_prepared(MpoGpModel& md, const PrepareWs& w, const ScorePlan& plan, c
 }
 
 }  // namespace
+
+// The blocked Cholesky of mpo_gp_prepare on a caller's padded matrix (gp_joint.hip factors
+// the sample covariance with it): the same kernels and step order, no L^-1.
+hipError_t mpo::blocked_chol(double* A, int np, double* Dinv, int32_t* info, hipStream_t s) {
+    (void)hipMemsetAsync(info, 0, sizeof(int32_t), s);
+    factor_blocks(A, np, Dinv, nullptr, info, s);
+    return hipGetLastError();
+}
 
 // ===========================================================================
 extern "C" {

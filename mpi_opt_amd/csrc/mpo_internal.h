@@ -24,6 +24,17 @@ void clear_error();
 // scoring entry points (gp.hip) refuse more with MPO_ENOTSUP.
 constexpr int kMaxObs = 2048;
 
+constexpr double kSqrt5 = 2.236067977499789696409173668731276235;
+
+// sklearn kernels.py:1715-1724 (nu = 2.5) times ConstantKernel: the factorisation's and the
+// joint posterior's Matern (gp.hip, gp_joint.hip).
+__device__ __forceinline__ double matern52(double r, double amp) {
+    // k^2 / 3 as a multiply by the rounded 1/3: within 1 ulp of sklearn's division,
+    // and an fp64 divide costs ~10 VALU ops per candidate-observation pair
+    const double k = r * kSqrt5;
+    return amp * ((1.0 + k + k * k * (1.0 / 3.0)) * exp(-k));
+}
+
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Carve consecutive 256-B aligned regions out of a caller workspace.
@@ -177,6 +188,12 @@ struct LmlRound {
 };
 bool lml_groupable(int n, int d);
 int lml_launch_rounds(const LmlRound* r, int count, hipStream_t s);
+
+// In-place lower blocked Cholesky (gp.hip: the bc_diag / bc_panel / bc_update steps of
+// mpo_gp_prepare) of the padded row-major A [np][np], np a multiple of 32: reads the lower
+// triangle and the full 32 x 32 diagonal blocks.  Dinv: np * 32 doubles of scratch.
+// *info (device) = 0, or the first failed column + 1.  All sums in a fixed order.
+hipError_t blocked_chol(double* A, int np, double* Dinv, int32_t* info, hipStream_t s);
 
 }  // namespace mpo
 

@@ -307,8 +307,63 @@ class DeviceGP:
             check(rc, "mpo_gp_polish_host")
         return [(x[r], float(f[r])) for r in range(B)]
 
-    def predict(self, Xc, return_std=True):
-        """skopt ``predict(X, return_std=True)`` -> numpy (mu, sd)."""
+    # -- joint posterior -------------------------------------------------------
+    def _ensure_joint_ws(self, m, s):
+        if m > _lib.MPO_JOINT_MAX:
+            raise ValueError(f"the joint posterior takes at most {_lib.MPO_JOINT_MAX} points, got {m}")
+        need = lib().mpo_gp_joint_ws_bytes(ctypes.byref(self.model), int(m), int(s))
+        if need == 0:
+            raise _lib.MpoError("mpo_gp_joint_ws_bytes rejected the shape")
+        if getattr(self, "_joint_ws", None) is None or self._joint_ws.numel() < need:
+            self._joint_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._joint_ws, need
+
+    def posterior_cov(self, cand):
+        """``mpo_gp_posterior_cov``: (mu (m,), cov (m, m)) as device tensors -- sklearn's
+        ``predict(X, return_cov=True)`` of the fitted skopt GP (no noise term;
+        ``diag(cov)`` is ``score``'s ``sd ** 2``).  cov is exactly symmetric."""
+        c = self.as_candidates(cand)
+        m = c.shape[0]
+        ws, wsb = self._ensure_joint_ws(m, 0)
+        mu = torch.empty(m, dtype=torch.float64, device=self.device)
+        cov = torch.empty(m, m, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().mpo_gp_posterior_cov(ctypes.byref(self.model), ptr(c), m, ptr(mu), ptr(cov), m, ptr(ws), wsb,
+                                             _lib.stream_handle(self.device)), "mpo_gp_posterior_cov")
+        return mu, cov
+
+    def sample(self, cand, z, jitter=1e-8, want_samples=True):
+        """``mpo_gp_sample``: correlated posterior draws at the candidates from the caller's
+        standard normal ``z`` (m, s): ``samples[r] = mu + y_std * Lc @ z[:, r]`` with
+        ``Lc Lc^T = cov / y_std^2 + jitter * amp * I``.  Returns device tensors
+        ``{"samples": (s, m) or None, "argmin": int64 (s,), "info": int}``; info != 0 (the
+        first failed column + 1 of the factorisation) leaves the other two meaningless."""
+        c = self.as_candidates(cand)
+        m = c.shape[0]
+        if isinstance(z, torch.Tensor):
+            zt = z.to(device=self.device, dtype=torch.float64).contiguous()
+        else:
+            zt = torch.from_numpy(np.ascontiguousarray(np.asarray(z, dtype=np.float64))).to(self.device)
+        if zt.ndim != 2 or zt.shape[0] != m or zt.shape[1] < 1:
+            raise ValueError(f"z must be ({m}, s >= 1), got {tuple(zt.shape)}")
+        s = zt.shape[1]
+        ws, wsb = self._ensure_joint_ws(m, s)
+        dev = self.device
+        samples = torch.empty(s, m, dtype=torch.float64, device=dev) if want_samples else None
+        argmin = torch.empty(s, dtype=torch.int64, device=dev)
+        info = torch.empty(1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            check(lib().mpo_gp_sample(ctypes.byref(self.model), ptr(c), m, ptr(zt), s, float(jitter), ptr(samples),
+                                      ptr(argmin), ptr(info), ptr(ws), wsb, _lib.stream_handle(dev)),
+                  "mpo_gp_sample")
+        return {"samples": samples, "argmin": argmin, "info": int(info.item())}
+
+    def predict(self, Xc, return_std=True, return_cov=False):
+        """skopt ``predict(X, return_std=True)`` -> numpy (mu, sd); with ``return_cov``
+        (sklearn's keyword) -> numpy (mu, cov) from ``posterior_cov``."""
+        if return_cov:
+            mu, cov = self.posterior_cov(Xc)
+            return mu.cpu().numpy(), cov.cpu().numpy()
         out = self.score(Xc, y_opt=0.0, acqs=("EI",), k=0, want_mu_sd=True, want_values=False)
         mu = out["mu"].cpu().numpy()
         sd = out["sd"].cpu().numpy()

@@ -93,6 +93,49 @@ class GPModel:
         mu, _ = self.dev.predict(np.atleast_2d(X))
         return mu
 
+    def predict(self, X, return_std=False, return_cov=False):
+        """sklearn's ``predict`` of the fitted skopt GP at the rows of ``X`` (transformed
+        space): mu, ``(mu, sd)`` or ``(mu, cov)`` as numpy arrays.  cov carries no noise term
+        (skopt zeroes the WhiteKernel after the fit); it comes from ``mpo_gp_posterior_cov``."""
+        if return_std and return_cov:
+            raise RuntimeError("At most one of return_std or return_cov can be requested.")
+        X = np.atleast_2d(np.asarray(X, dtype=float))
+        if return_cov:
+            return self.dev.predict(X, return_cov=True)
+        mu, sd = self.dev.predict(X)
+        return (mu, sd) if return_std else mu
+
+    def sample_y(self, X, n_samples=1, random_state=0):
+        """sklearn's ``sample_y``: ``n_samples`` joint draws of the posterior at the rows of
+        ``X`` (transformed space), shape ``(m, n_samples)``.  The draws are
+        ``mu + L z`` with ``z = RandomState(random_state).standard_normal((m, n_samples))``
+        and ``L`` the device Cholesky factor of the posterior covariance
+        (``mpo_gp_sample``; relative jitter 1e-8, then 1e-6, then 1e-4, then
+        ``LinAlgError``).  The distribution is sklearn's; the bits are not: sklearn draws
+        through ``multivariate_normal``'s SVD of the covariance."""
+        X = np.atleast_2d(np.asarray(X, dtype=float))
+        z = check_random_state(random_state).standard_normal((X.shape[0], int(n_samples)))
+        out = sample_with_ladder(self.dev, X, z)
+        return out["samples"].cpu().numpy().T
+
+
+#: relative jitters (times amp) tried in turn on the sample covariance's diagonal
+JITTER_LADDER = (1e-8, 1e-6, 1e-4)
+
+
+def sample_with_ladder(dev, cand, z, want_samples=True):
+    """``DeviceGP.sample`` at the first jitter of ``JITTER_LADDER`` whose factorisation
+    succeeds (``info == 0``); the result carries it as ``"jitter"``.  ``LinAlgError`` when
+    none does."""
+    for jitter in JITTER_LADDER:
+        out = dev.sample(cand, z, jitter=jitter, want_samples=want_samples)
+        if out["info"] == 0:
+            out["jitter"] = jitter
+            return out
+    raise np.linalg.LinAlgError(
+        f"the posterior covariance of {len(z)} points is not positive definite at jitter {JITTER_LADDER[-1]:g} "
+        f"(device Cholesky failed at column {out['info'] - 1})")
+
 
 def polish_lockstep(model, starts, acqs, y_opt, xi, kappa, bounds, maxiter=20, driver="native"):
     """skopt's acquisition polish: ``fmin_l_bfgs_b(gaussian_acquisition_1D, x0,
@@ -194,7 +237,9 @@ def _gather_winners(X, index_lists):
     return dict(zip(idx.tolist(), rows))
 
 
-STRATEGIES = ("cl_min", "cl_mean", "cl_max")
+#: ask(n, strategy): skopt's three constant liars, then "thompson" (an addition of this
+#: build, last so that the encoded index of the others does not move)
+STRATEGIES = ("cl_min", "cl_mean", "cl_max", "thompson")
 #: Optimizer(lie_refit=...): refit the hyper-parameters for every lie of an ask(n) batch
 #: (skopt) or for none of them
 LIE_REFIT = ("every", "never")
@@ -242,8 +287,13 @@ class ChainJob:
         self.trace = opt.trace is not None
         # LPT weight: a refit costs ~n^2 at these sizes (the LML's n^3 work is spread
         # over n/16 workgroups); one refit per lie once the initial points are spent
-        n0 = len(self.yi)
-        self.cost = float(sum((n0 + i + 1) ** 2 for i in range(self.n_points)))
+        self.cost = self._cost(len(self.yi), self.n_points, strategy)
+
+    @staticmethod
+    def _cost(n0, n_points, strategy):
+        if strategy == "thompson":      # one refit for the whole batch
+            return float((n0 + 1) ** 2)
+        return float(sum((n0 + i + 1) ** 2 for i in range(n_points)))
 
     # ---- fixed-layout form for the tensor collectives (blocks.DistributedEvaluator) ----
     META = 10   # int64 words per job: n, D, has_gains, n_initial_points, seed, n_points, strategy, trace, n_init, blob
@@ -299,7 +349,7 @@ class ChainJob:
         job.n_initial_points = nip
         job.seed = seed
         job.n_points, job.strategy, job.trace = npts, STRATEGIES[strat], False
-        job.cost = float(sum((n + i + 1) ** 2 for i in range(npts)))
+        job.cost = cls._cost(n, npts, job.strategy)
         return job
 
     def copy_optimizer(self, device=None, scorer=None):
@@ -316,6 +366,8 @@ class ChainJob:
     def run(self, device=None, scorer=None):
         """The batch: (list of points, the copy's refit trace or None)."""
         opt = self.copy_optimizer(device, scorer)
+        if self.strategy == "thompson":
+            return _thompson_batch(opt, self.n_points), opt.trace
         return _lie_loop(opt, self.n_points, self.strategy), opt.trace
 
 
@@ -340,6 +392,80 @@ def _lie_loop(opt, n_points, strategy):
         for m in opt.models[:-1]:
             m._dev = None
     return X
+
+
+def _thompson_batch(opt, n_points):
+    """A Thompson-sampling batch on the copy ``opt`` (NOT skopt's semantics): the copy's
+    remaining initial points as the ``cl_min`` loop takes them, then ONE joint draw of the
+    newest model's posterior over ``n_ts_points`` candidates per remaining point and the
+    argmin of each draw -- no lie, no refit, no polish, no gp_hedge update."""
+    X = []
+    while len(X) < n_points and (opt._n_initial_points > 0 or opt.base_estimator_ == "dummy"):
+        x = opt._ask()
+        X.append(x)
+        opt._tell(x, np.min(opt.yi) if opt.yi else 0.0, append=opt.lie_refit == "never")
+    r = n_points - len(X)
+    if r > 0:
+        X.extend(_thompson_step(opt, r))
+    return X
+
+
+def thompson_dedupe(argmin, row_of):
+    """Draw k takes its lowest-sample candidate that no earlier draw took, the draws in
+    order.  ``argmin[k]`` is the draw's argmin over all candidates; ``row_of(k)`` fetches
+    its samples (called for colliding draws only).  Returns the picks."""
+    taken, picks = set(), []
+    for k, i in enumerate(int(v) for v in argmin):
+        if i in taken:
+            row = np.array(row_of(k), dtype=float)
+            row[sorted(taken)] = np.inf
+            i = int(np.argmin(row))
+        taken.add(i)
+        picks.append(i)
+    return picks
+
+
+def _thompson_step(opt, r):
+    """``r`` points from one Thompson step on the newest model of ``opt``."""
+    import torch
+
+    n_ts = int(opt.acq_optimizer_kwargs.get("n_ts_points", 2048))
+    if n_ts > _lib.MPO_JOINT_MAX:
+        raise ValueError(f"n_ts_points = {n_ts} exceeds the joint posterior's {_lib.MPO_JOINT_MAX} points")
+    if r > n_ts:
+        raise ValueError(f"a Thompson batch of {r} points needs at least as many candidates, n_ts_points = {n_ts}")
+    est = opt.models[-1]
+    t0 = time.perf_counter()
+    cand_seed = None
+    if opt.candidates == "device":
+        from .candidates import sample_transformed
+
+        cand_seed = int(opt.rng.randint(0, np.iinfo(np.int32).max))
+        C = sample_transformed(opt.space, n_ts, cand_seed, device=opt.device)
+    else:
+        C = opt.space.rvs_transformed(n_samples=n_ts, random_state=opt.rng)
+    Z = opt.rng.standard_normal((n_ts, r))
+    t1 = time.perf_counter()
+    out = sample_with_ladder(est.dev, C, Z)
+    argmin = out["argmin"].cpu().numpy()
+    t2 = time.perf_counter()
+    picks = thompson_dedupe(argmin, lambda k: out["samples"][k].cpu().numpy())
+    if cand_seed is not None:
+        rows = C[torch.as_tensor(picks, device=C.device)].cpu().numpy()
+    else:
+        rows = np.asarray(C)[picks]
+    t3 = time.perf_counter()
+    # host-clock split of the step, on the copy (scripts/thompson_probe.py reports it)
+    opt.thompson_times = {"candidates_s": t1 - t0, "sample_s": t2 - t1, "dedupe_s": t3 - t2}
+    if opt.trace is not None:
+        rec = {"thompson": True, "theta": (est.amp, est.length_scale.copy(), est.noise), "z": Z,
+               "jitter": out["jitter"], "picks": list(picks)}
+        if cand_seed is not None:
+            rec["cand_seed"] = cand_seed
+        else:
+            rec["cand"] = np.array(C)
+        opt.trace.append(rec)
+    return [list(x) for x in opt.space.inverse_transform(rows)]
 
 
 class OptimizeResult(dict):
@@ -369,13 +495,25 @@ class Optimizer:
     (seed, row) (``mpo_space_sample``, :mod:`~mpi_opt_amd.candidates`).  Not skopt's
     stream: other bits, other RandomState draws; the same distribution up to a set of
     measure zero (Reals exclude the upper bound and skip the host's
-    inverse_transform / transform round trip of a few ulp)."""
+    inverse_transform / transform round trip of a few ulp).
+
+    ``batch_strategy`` (one of ``STRATEGIES``, an addition of this build): the strategy of
+    an ``ask(n)`` that names none; "cl_min" is skopt's default.  "thompson" departs from
+    skopt: one fit, one joint draw of n posterior samples over
+    ``acq_optimizer_kwargs["n_ts_points"]`` (2048, at most 4096) candidates
+    (``mpo_gp_sample``), each point the argmin of its sample among the candidates no earlier
+    draw took -- no lie, no refit, no polish, no gp_hedge update for the batch."""
 
     def __init__(self, dimensions, base_estimator="gp", n_random_starts=None, n_initial_points=10,
                  initial_point_generator="random", acq_func="gp_hedge", acq_optimizer="auto",
                  random_state=None, model_queue_size=None, acq_func_kwargs=None, acq_optimizer_kwargs=None,
                  device=None, _gp_seed=None, scorer=None, chain_executor=None, lie_refit="every",
-                 candidates="host"):
+                 candidates="host", batch_strategy="cl_min"):
+        if batch_strategy not in STRATEGIES:
+            raise ValueError(f"batch_strategy {batch_strategy!r}: one of {STRATEGIES}")
+        # the strategy of ask(n) calls that name none (the reference's Coordinator.ask does
+        # not).  "thompson" is NOT the reference's semantics.
+        self.batch_strategy = batch_strategy
         if lie_refit not in LIE_REFIT:
             raise ValueError(f"lie_refit {lie_refit!r}: one of {LIE_REFIT}")
         if candidates not in CANDIDATES:
@@ -436,6 +574,7 @@ class Optimizer:
         d.setdefault("chain_executor", None)
         d.setdefault("lie_refit", "every")
         d.setdefault("candidates", "host")
+        d.setdefault("batch_strategy", "cl_min")
         self.__dict__.update(d)
 
     def _config(self):
@@ -444,21 +583,32 @@ class Optimizer:
                     n_initial_points=self.n_initial_points_, initial_point_generator=self._initial_point_generator,
                     acq_func=self.acq_func, acq_optimizer=self.acq_optimizer, acq_func_kwargs=self.acq_func_kwargs,
                     acq_optimizer_kwargs=self.acq_optimizer_kwargs, _gp_seed=self._gp_seed,
-                    lie_refit=self.lie_refit, candidates=self.candidates)
+                    lie_refit=self.lie_refit, candidates=self.candidates, batch_strategy=self.batch_strategy)
 
     # ---- ask -------------------------------------------------------------------
     def copy(self, random_state=None):
         return ChainJob(self, random_state, 0, "cl_min").copy_optimizer(self.device, self.scorer)
 
-    def ask(self, n_points=None, strategy="cl_min"):
+    def ask(self, n_points=None, strategy=None):
         if n_points is None:
             return self._ask()
-        if strategy not in ("cl_min", "cl_mean", "cl_max"):
+        if strategy is None:
+            strategy = self.batch_strategy
+        if strategy not in STRATEGIES:
             raise ValueError(f"strategy {strategy!r}")
+        if strategy == "thompson" and self.base_estimator_ == "gp":
+            # refused here, before the copy's fit (_thompson_step checks again)
+            n_ts = self.acq_optimizer_kwargs.get("n_ts_points", 2048)
+            if n_ts > _lib.MPO_JOINT_MAX:
+                raise ValueError(f"n_ts_points = {n_ts} exceeds the joint posterior's {_lib.MPO_JOINT_MAX} points")
+            if n_points - max(self._n_initial_points, 0) > n_ts:
+                raise ValueError(f"a Thompson batch of {n_points} points needs at least as many candidates, "
+                                 f"n_ts_points = {n_ts}")
         if (n_points, strategy) in self.cache_:
             return self.cache_[(n_points, strategy)]
         if self.base_estimator_ == "gp" and self._n_initial_points - n_points <= 0:
-            _check_gp_size(len(self.yi), n_points)      # every lie is told to the copy, the last one too
+            # every lie is told to the copy, the last one too; a Thompson batch tells none
+            _check_gp_size(len(self.yi), 0 if strategy == "thompson" else n_points)
         job = ChainJob(self, self.rng.randint(0, np.iinfo(np.int32).max), n_points, strategy)
         if self.chain_executor is not None:
             X = self.chain_executor.submit(job)

@@ -110,6 +110,11 @@ def make_parser():
                         "skopt's and the reference's semantics) or never (NOT the reference's semantics: the "
                         "batch keeps the theta of the last told model and appends each lie to its posterior "
                         "in O(n^2); tells always refit)")
+    p.add_argument("--batch-strategy", default="cl_min", choices=["cl_min", "thompson"], dest="batch_strategy",
+                   help="how an ask batch is made: cl_min (the constant-liar batch, skopt's and the reference's "
+                        "semantics) or thompson (NOT the reference's semantics: one fit per batch, one joint "
+                        "draw of the posterior over n_ts_points candidates per point, each point the argmin of "
+                        "its draw; no lies, no refits, no polish)")
     return p
 
 
@@ -235,6 +240,8 @@ def run_search(args, x=None, y=None, log=print, progress=None, on_population=Non
     opt_kw = {"device": dev, "acq_optimizer_kwargs": {"n_points": args.ei_candidates}}
     if args.lie_refit != "every":
         opt_kw["lie_refit"] = args.lie_refit              # fixed-theta ask batches (not skopt's semantics)
+    if args.batch_strategy != "cl_min":
+        opt_kw["batch_strategy"] = args.batch_strategy    # Thompson ask batches (not skopt's semantics)
     if args.candidate_source != "host":
         opt_kw["candidates"] = args.candidate_source      # device-drawn candidates (not skopt's stream)
     if chains is not None:
