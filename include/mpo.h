@@ -256,11 +256,14 @@ int mpo_gp_acq_grad_host(const MpoGpModel* model, const double* x_host, int batc
  * runs in a fixed order, so two calls give the same bits.
  * ---------------------------------------------------------------------- */
 #define MPO_JOINT_MAX 4096
+/* The most draws of one mpo_gp_sample call: 16 x 65535, the y extent of the sampling
+ * kernel's grid (16 draws per workgroup). */
+#define MPO_JOINT_SMAX 1048560
 
 /* Workspace bytes of mpo_gp_posterior_cov (s = 0) or mpo_gp_sample (s >= 1 draws) over m
  * query points: V = K* W^T [m32][np16], and for s >= 1 the [m32][m32] matrix that is
  * factored (m32 = m rounded up to 32; 194 MiB at n = 2048, m = 4096).  0 if unsupported:
- * null or malformed model, n > 2048, m < 1, m > MPO_JOINT_MAX, s < 0. */
+ * null or malformed model, n > 2048, m < 1, m > MPO_JOINT_MAX, s < 0, s > MPO_JOINT_SMAX. */
 size_t mpo_gp_joint_ws_bytes(const MpoGpModel* model, int m, int s);
 
 /* mu [m] (or NULL: not written) and cov [m][ldc]:
@@ -285,10 +288,10 @@ int mpo_gp_posterior_cov(const MpoGpModel* model, const double* cand, int m,
  * argmin [s] may each be NULL (not written).  *info (device int32): 0, or the first
  * failed column + 1 as mpo_chol_f64 reports it -- the outputs are then meaningless and
  * the caller retries with a larger jitter.
- * MPO_ENOTSUP: m > MPO_JOINT_MAX or n > 2048.  MPO_EINVAL: a null model, cand, z, info or
- * workspace, m < 1, s < 1, a negative or non-finite jitter, a malformed model, a
- * workspace smaller than mpo_gp_joint_ws_bytes(model, m, s).  All checks run on the host
- * before any launch.  Only enqueues work: no allocation, no host synchronisation.
+ * MPO_ENOTSUP: m > MPO_JOINT_MAX, n > 2048 or s > MPO_JOINT_SMAX.  MPO_EINVAL: a null model,
+ * cand, z, info or workspace, m < 1, s < 1, a negative or non-finite jitter, a malformed
+ * model, a workspace smaller than mpo_gp_joint_ws_bytes(model, m, s).  All checks run on the
+ * host before any launch.  Only enqueues work: no allocation, no host synchronisation.
  * sklearn's sample_y draws through multivariate_normal's SVD: the same distribution,
  * other bits.
  * NOT the reference's semantics: skopt's ask(n_points) (Coordinator.ask,

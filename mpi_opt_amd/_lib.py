@@ -18,6 +18,7 @@ MPO_ACQ_PI = 2
 MPO_ACQ_LCB = 4
 MPO_TOPK_MAX = 8
 MPO_JOINT_MAX = 4096
+MPO_JOINT_SMAX = 1048560
 ACQ_FLAGS = {"EI": MPO_ACQ_EI, "PI": MPO_ACQ_PI, "LCB": MPO_ACQ_LCB}
 # MpoCnnSpec.options: option3's --loss / --optimizer (include/mpo.h MPO_LOSS_* | MPO_OPT_*)
 LOSS_CODES = {"binary_crossentropy": 0x0, "categorical_crossentropy": 0x1}

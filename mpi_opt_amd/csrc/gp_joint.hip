@@ -335,7 +335,9 @@ int launch_cov(const MpoGpModel* md, int m, int rows, const JointWs& w, double s
 extern "C" {
 
 size_t mpo_gp_joint_ws_bytes(const MpoGpModel* model, int m, int s) {
-    if (!model || m < 1 || m > MPO_JOINT_MAX || s < 0 || !shape_ok(model) || model->n > mpo::kMaxObs) return 0;
+    if (!model || m < 1 || m > MPO_JOINT_MAX || s < 0 || s > MPO_JOINT_SMAX || !shape_ok(model) ||
+        model->n > mpo::kMaxObs)
+        return 0;
     return carve_joint_ws(nullptr, model->np16, model->dp, m, s).used + 256;
 }
 
@@ -362,6 +364,10 @@ int mpo_gp_sample(const MpoGpModel* model, const double* cand, int m, const doub
     if (const int rc = joint_check(who, model, cand, m)) return rc;
     MPO_CHECK_ARG(z && info && ws, "%s: null z/info/workspace", who);
     MPO_CHECK_ARG(s >= 1, "%s: s=%d must be >= 1", who, s);
+    if (s > MPO_JOINT_SMAX) {   // joint_sample_kernel's grid y is ceil(s / 16) <= 65535
+        mpo::set_error("%s: s=%d outside the supported s <= %d", who, s, MPO_JOINT_SMAX);
+        return MPO_ENOTSUP;
+    }
     MPO_CHECK_ARG(jitter >= 0.0 && std::isfinite(jitter), "%s: jitter must be finite and >= 0", who);
     const size_t need = mpo_gp_joint_ws_bytes(model, m, s);
     MPO_CHECK_ARG(ws_bytes >= need, "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);

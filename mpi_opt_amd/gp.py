@@ -347,6 +347,8 @@ class DeviceGP:
         if zt.ndim != 2 or zt.shape[0] != m or zt.shape[1] < 1:
             raise ValueError(f"z must be ({m}, s >= 1), got {tuple(zt.shape)}")
         s = zt.shape[1]
+        if s > _lib.MPO_JOINT_SMAX:
+            raise ValueError(f"one call draws at most {_lib.MPO_JOINT_SMAX} samples, got {s}")
         ws, wsb = self._ensure_joint_ws(m, s)
         dev = self.device
         samples = torch.empty(s, m, dtype=torch.float64, device=dev) if want_samples else None
