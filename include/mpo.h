@@ -304,6 +304,97 @@ int mpo_gp_sample(const MpoGpModel* model, const double* cand, int m,
                   int32_t* info, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * PATHWISE posterior samples of a prepared model (Matheron's rule; Wilson et al. 2020,
+ * "Efficiently sampling functions from Gaussian process posteriors"): a draw is a
+ * function that can be evaluated at any point -- a prior draw from F random Fourier
+ * features plus a data-dependent correction through the factor the model holds.  No
+ * m x m matrix, no factorisation, no jitter and no cap on m.  With c = x / ls,
+ * phi_j(x) = cos(omega_j . c + phase_j), scale = sqrt(2 amp / F) and the caller's
+ *   omega [F][d]  frequencies in the length-scaled space, the spectral law of the
+ *                 unit-length-scale Matern-5/2 kernel: z sqrt(5 / u), z ~ N(0, I_d),
+ *                 u ~ chi^2_5
+ *   phase [F]     uniform on [0, 2 pi)
+ *   w [F][s], eps [n][s]   standard normal
+ * the s paths are
+ *   resid[:, r] = scale Phi(X) w[:, r] + sqrt(noise + 1e-10) eps[:, r]
+ *   v[:, r]     = alpha - W^T (W resid[:, r])
+ *   coef        = [scale w ; v]                                          [(F + n)][s]
+ *   f_r(x)      = y_mean + y_std (sum_j phi_j(x) coef[j][r]
+ *                                 + sum_i amp Matern52(|c - xs_i|) coef[F + i][r])
+ * The conditioning on the data is exact; the prior is a random-feature APPROXIMATION of
+ * the Matern-5/2 prior.  With an exact prior f_r has the mean and the noise-free
+ * covariance of mpo_gp_posterior_cov.  Reads the model's plain W, xs, alpha and ls only:
+ * any prepared, appended or copied model of n <= 2048 observations is served, whatever
+ * its scoring path.  Every sum runs in a fixed order: two calls give the same bits, and
+ * the value of a point under a draw does not depend on m, on the rows around it or on
+ * the draw range of the call.
+ * NOT the reference's semantics and not exact Thompson sampling: skopt's ask(n_points)
+ * (Coordinator.ask, coordinator.py:46-50) is a constant-liar batch, and sklearn's
+ * sample_y (_gpr.py:472-507) draws from the exact joint posterior; these entry points
+ * serve the opt-in acq_optimizer_kwargs["ts_sampler"] = "paths" Thompson batch and
+ * GPModel.sample_paths.
+ * ---------------------------------------------------------------------- */
+#define MPO_PATHS_FMAX 4096      /* random features per set of paths   */
+#define MPO_PATHS_SMAX 1024      /* draws per set of paths             */
+
+/* A prepared set of paths (host struct): device pointers into the prepare workspace. */
+typedef struct MpoGpPaths {
+    int32_t F;             /* features                                           */
+    int32_t s;             /* draws                                              */
+    int32_t n;             /* observations of the model the paths were built for */
+    int32_t dp;            /* its padded dimensions                              */
+    int32_t Fp;            /* F rounded up to 16                                 */
+    int32_t Kp;            /* Fp + np16 rounded up to 64: rows of coef           */
+    int32_t sp;            /* s rounded up to 16, plus 16: row stride of coef    */
+    int32_t reserved;
+    const double* omega;   /* [Fp][dp] zero-padded                               */
+    const double* phase;   /* [Fp]                                               */
+    const double* coef;    /* [Kp][sp] rows [0, F): scale w; [Fp, Fp + n): v; 0 elsewhere */
+} MpoGpPaths;
+
+/* Workspace bytes of mpo_gp_paths_prepare: the paths plus Phi(X) [n][F] and two [n][s]
+ * intermediates (145 MiB at n = 2048, F = 4096, s = 1024; 10 MiB at 256, 2048, 256).  0 if
+ * unsupported: a null or malformed model, n > 2048, F < 1, F > MPO_PATHS_FMAX, s < 1,
+ * s > MPO_PATHS_SMAX. */
+size_t mpo_gp_paths_ws_bytes(const MpoGpModel* model, int F, int s);
+
+/* Build coef by the formulas above into `ws`; `paths` receives pointers into it, so `ws`
+ * stays alive while the paths are used.  `noise` is the WhiteKernel value the model was
+ * prepared with.  omega, phase, w, eps: device.
+ * MPO_ENOTSUP: n > 2048, F > MPO_PATHS_FMAX or s > MPO_PATHS_SMAX.  MPO_EINVAL: a null
+ * pointer, F < 1, s < 1, a negative or non-finite noise, a malformed model, a workspace
+ * smaller than mpo_gp_paths_ws_bytes(model, F, s).  All checks run on the host before any
+ * launch.  Only enqueues work: no allocation, no host synchronisation, capturable in a
+ * graph. */
+int mpo_gp_paths_prepare(const MpoGpModel* model, double noise,
+                         const double* omega /*[F][d]*/, const double* phase /*[F]*/,
+                         const double* w /*[F][s]*/, const double* eps /*[n][s]*/, int F, int s,
+                         MpoGpPaths* paths, void* ws, size_t ws_bytes, void* stream);
+
+/* Workspace bytes of mpo_gp_paths_eval (the workgroups' (min, index) partials); 0 if
+ * unsupported: a null or malformed model or paths, m < 1, n_draws outside [1, s]. */
+size_t mpo_gp_paths_eval_ws_bytes(const MpoGpModel* model, const MpoGpPaths* paths, int64_t m, int n_draws);
+
+/* Draws first_draw .. first_draw + n_draws - 1 at the m candidates (transformed space,
+ * [m][d] device), one fused kernel: per tile of 64 candidates the operand
+ * [cos(omega_j . c + phase_j) | amp Matern52(|c - xs_i|)] is computed once, panel by panel,
+ * and multiplied into coef on fp64 MFMA for every draw of the call.
+ *   samples[k][i]  draw first_draw + k at candidate i              ([n_draws][m] or NULL)
+ *   argmin[k]      the lowest index among the smallest samples[k][.]  (np.argmin; or NULL)
+ *   minval[k]      that sample, bit for bit                                     (or NULL)
+ * MPO_ENOTSUP: n > 2048, F > MPO_PATHS_FMAX or s > MPO_PATHS_SMAX.  MPO_EINVAL: a null
+ * model, paths, cand or workspace, m < 1, a draw range outside [0, s), a malformed model
+ * or paths struct (or paths of another model shape), a workspace smaller than
+ * mpo_gp_paths_eval_ws_bytes(model, paths, m, n_draws).  All checks run on the host before
+ * any launch.  Only enqueues work: no allocation, no host synchronisation, no atomics,
+ * capturable in a graph.  MPO_PATHS_GRID=<workgroups> lowers the cap on the grid's x extent
+ * (512 workgroups per 256 draws; a test knob: the values do not depend on it). */
+int mpo_gp_paths_eval(const MpoGpModel* model, const MpoGpPaths* paths,
+                      const double* cand /*[m][d]*/, int64_t m, int first_draw, int n_draws,
+                      double* samples /*[n_draws][m] or NULL*/, int64_t* argmin /*[n_draws] or NULL*/,
+                      double* minval /*[n_draws] or NULL*/, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Acquisition candidates drawn on the device (opt-in: Optimizer(candidates="device")).
  * skopt draws the n_points candidates of every ask on the host, column by column from
  * one RandomState (Space.rvs + transform, reached from Coordinator.ask,

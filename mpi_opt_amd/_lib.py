@@ -19,6 +19,8 @@ MPO_ACQ_LCB = 4
 MPO_TOPK_MAX = 8
 MPO_JOINT_MAX = 4096
 MPO_JOINT_SMAX = 1048560
+MPO_PATHS_FMAX = 4096
+MPO_PATHS_SMAX = 1024
 ACQ_FLAGS = {"EI": MPO_ACQ_EI, "PI": MPO_ACQ_PI, "LCB": MPO_ACQ_LCB}
 # MpoCnnSpec.options: option3's --loss / --optimizer (include/mpo.h MPO_LOSS_* | MPO_OPT_*)
 LOSS_CODES = {"binary_crossentropy": 0x0, "categorical_crossentropy": 0x1}
@@ -39,6 +41,14 @@ class MpoGpModel(ctypes.Structure):
         ("xs", ctypes.c_void_p), ("ls", ctypes.c_void_p), ("alpha", ctypes.c_void_p),
         ("wfrag", ctypes.c_void_p), ("L", ctypes.c_void_p), ("W", ctypes.c_void_p),
         ("info", ctypes.c_void_p), ("wmeta", ctypes.c_void_p), ("xb", ctypes.c_void_p),
+    ]
+
+
+class MpoGpPaths(ctypes.Structure):
+    _fields_ = [
+        ("F", ctypes.c_int32), ("s", ctypes.c_int32), ("n", ctypes.c_int32), ("dp", ctypes.c_int32),
+        ("Fp", ctypes.c_int32), ("Kp", ctypes.c_int32), ("sp", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("omega", ctypes.c_void_p), ("phase", ctypes.c_void_p), ("coef", ctypes.c_void_p),
     ]
 
 
@@ -113,6 +123,12 @@ SIGNATURES = {
     "mpo_gp_joint_ws_bytes": (_SZ, [ctypes.POINTER(MpoGpModel), _I, _I]),
     "mpo_gp_posterior_cov": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _P, _I, _P, _SZ, _P]),
     "mpo_gp_sample": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _I, _D, _P, _P, _P, _P, _SZ, _P]),
+    "mpo_gp_paths_ws_bytes": (_SZ, [ctypes.POINTER(MpoGpModel), _I, _I]),
+    "mpo_gp_paths_prepare": (_I, [ctypes.POINTER(MpoGpModel), _D, _P, _P, _P, _P, _I, _I, ctypes.POINTER(MpoGpPaths),
+                                  _P, _SZ, _P]),
+    "mpo_gp_paths_eval_ws_bytes": (_SZ, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpPaths), _I64, _I]),
+    "mpo_gp_paths_eval": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpPaths), _P, _I64, _I, _I, _P, _P, _P,
+                               _P, _SZ, _P]),
     "mpo_space_sample": (_I, [ctypes.POINTER(MpoDimDesc), _I, _I, ctypes.c_uint64, _I64, _I64, _P, _P]),
     "mpo_lbfgsb_batched": (_I, [_I, _I, _P, _P, ctypes.POINTER(MpoLbfgsbOptions), FG_BATCH_FN, _P, _P, _P, _P,
                                 _P]),

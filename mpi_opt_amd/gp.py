@@ -360,6 +360,21 @@ class DeviceGP:
                   "mpo_gp_sample")
         return {"samples": samples, "argmin": argmin, "info": int(info.item())}
 
+    # -- pathwise samples --------------------------------------------------------
+    def paths(self, omega, phase, w, eps, noise=None):
+        """``mpo_gp_paths_prepare``: the s sample paths of the random inputs ``omega`` (F, d),
+        ``phase`` (F,), ``w`` (F, s), ``eps`` (n, s) (:func:`mpi_opt_amd.paths.draw_paths`) as a
+        :class:`~mpi_opt_amd.paths.DevicePaths`.  The prior is a random-feature approximation
+        (NOT the reference's semantics).  ``noise`` defaults to the model's own; a scoring-only
+        ``from_factor`` copy holds none and takes it explicitly."""
+        from .paths import DevicePaths
+
+        if noise is None:
+            if not hasattr(self, "noise"):
+                raise ValueError("a scoring-only DeviceGP (from_factor) holds no noise: pass noise=")
+            noise = self.noise
+        return DevicePaths(self, omega, phase, w, eps, noise)
+
     def predict(self, Xc, return_std=True, return_cov=False):
         """skopt ``predict(X, return_std=True)`` -> numpy (mu, sd); with ``return_cov``
         (sklearn's keyword) -> numpy (mu, cov) from ``posterior_cov``."""

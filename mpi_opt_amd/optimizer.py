@@ -118,6 +118,28 @@ class GPModel:
         out = sample_with_ladder(self.dev, X, z)
         return out["samples"].cpu().numpy().T
 
+    def sample_paths(self, n_samples=1, n_features=2048, random_state=0):
+        """The continuous counterpart of ``sample_y`` (NOT the reference's semantics):
+        ``n_samples`` posterior sample paths as a callable ``paths(X) -> ndarray
+        (m, n_samples)`` that can be evaluated at any rows ``X`` (transformed space), any
+        number of times.  Pathwise conditioning (``mpo_gp_paths_prepare`` / ``_eval``): the
+        conditioning on the data is exact, the Matern-5/2 prior is approximated by
+        ``n_features`` random Fourier features drawn by
+        ``draw_paths(RandomState(random_state), ...)``."""
+        from .paths import check_sizes, draw_paths
+
+        n_samples, n_features = int(n_samples), int(n_features)
+        check_sizes(n_features, n_samples)
+        n, d = self.Xt.shape
+        dp = self.dev.paths(*draw_paths(check_random_state(random_state), n_features, d, n_samples, n))
+
+        def paths(X):
+            X = np.atleast_2d(np.asarray(X, dtype=float))
+            return dp.eval(X, want_samples=True)["samples"].cpu().numpy().T
+
+        paths.device_paths = dp
+        return paths
+
 
 #: relative jitters (times amp) tried in turn on the sample covariance's diagonal
 JITTER_LADDER = (1e-8, 1e-6, 1e-4)
@@ -425,15 +447,112 @@ def thompson_dedupe(argmin, row_of):
     return picks
 
 
+#: acq_optimizer_kwargs["ts_sampler"]: how a Thompson batch draws its samples.  "joint" is
+#: mpo_gp_sample (the exact joint posterior over <= MPO_JOINT_MAX candidates); "paths" is
+#: mpo_gp_paths_* (pathwise conditioning: a random-feature prior, any number of candidates)
+TS_SAMPLERS = ("joint", "paths")
+
+
+def thompson_config(kwargs, n_points, r):
+    """``(ts_sampler, n_ts_points, n_ts_features)`` of a Thompson step of ``r`` points under
+    ``acq_optimizer_kwargs`` (``n_points``: the optimizer's candidate count, the default of
+    ``n_ts_points`` for the "paths" sampler), or the ``ValueError`` that refuses it.  Host
+    arithmetic only: ``ask`` calls it before any fit, ``_thompson_step`` again."""
+    sampler = kwargs.get("ts_sampler", "joint")
+    if sampler not in TS_SAMPLERS:
+        raise ValueError(f"ts_sampler {sampler!r}: one of {TS_SAMPLERS}")
+    n_feat = int(kwargs.get("n_ts_features", 2048))
+    if sampler == "joint":
+        n_ts = int(kwargs.get("n_ts_points", 2048))
+        if n_ts > _lib.MPO_JOINT_MAX:
+            raise ValueError(f"n_ts_points = {n_ts} exceeds the joint posterior's {_lib.MPO_JOINT_MAX} points")
+    else:
+        n_ts = int(kwargs.get("n_ts_points", n_points))
+        if not 1 <= n_feat <= _lib.MPO_PATHS_FMAX:
+            raise ValueError(f"n_ts_features = {n_feat} outside 1 .. {_lib.MPO_PATHS_FMAX}")
+        if r > _lib.MPO_PATHS_SMAX:
+            raise ValueError(f"a pathwise Thompson batch draws at most {_lib.MPO_PATHS_SMAX} points, got {r}")
+    if r > n_ts:
+        raise ValueError(f"a Thompson batch of {r} points needs at least as many candidates, n_ts_points = {n_ts}")
+    return sampler, n_ts, n_feat
+
+
+def _thompson_paths_step(opt, r, n_ts, n_feat):
+    """``_thompson_step`` under ``ts_sampler="paths"`` (NOT the reference's semantics, and not
+    exact Thompson sampling: the prior of the draws is a random-feature approximation):
+    candidates from the configured source, ``draw_paths`` from the copy's RandomState, one
+    ``mpo_gp_paths_prepare`` and one ``mpo_gp_paths_eval``.  No jitter ladder."""
+    import torch
+
+    from .paths import SAMPLE_ROWS_MAX_BYTES, draw_paths
+
+    est = opt.models[-1]
+    t0 = time.perf_counter()
+    cand_seed = None
+    if opt.candidates == "device":
+        from .candidates import sample_transformed
+
+        cand_seed = int(opt.rng.randint(0, np.iinfo(np.int32).max))
+        C = sample_transformed(opt.space, n_ts, cand_seed, device=opt.device)
+    else:
+        C = opt.space.rvs_transformed(n_samples=n_ts, random_state=opt.rng)
+    t1 = time.perf_counter()
+    n, d = est.Xt.shape
+    omega, phase, w, eps = draw_paths(opt.rng, n_feat, d, r, n)
+    t2 = time.perf_counter()
+    dev = est.dev
+    Ct = dev.as_candidates(C)
+    paths = dev.paths(omega, phase, w, eps)
+    torch.cuda.synchronize(dev.device)
+    t3 = time.perf_counter()
+    with_rows = r * n_ts * 8 <= SAMPLE_ROWS_MAX_BYTES
+    out = paths.eval(Ct, want_samples=with_rows)
+    argmin = out["argmin"].cpu().numpy()
+    t4 = time.perf_counter()
+    if with_rows:
+        picks = thompson_dedupe(argmin, lambda k: out["samples"][k].cpu().numpy())
+    else:
+        # the same rule with the colliding draw's row evaluated again and masked on the device.  A
+        # draw's row is the same bits in any call (mpo_gp_paths_eval), so the evaluation takes the
+        # draws after it along while their rows fit the same bytes (one draw alone when none does):
+        # an evaluation builds its cosine / Matern operand once whatever the number of draws
+        block = max(1, SAMPLE_ROWS_MAX_BYTES // (n_ts * 8))
+        first, cached = 0, None
+        taken, picks = [], []
+        for k, i in enumerate(int(v) for v in argmin):
+            if i in taken:
+                if cached is None or not first <= k < first + cached.shape[0]:
+                    first = k
+                    cached = paths.eval(Ct, first_draw=k, n_draws=min(block, r - k), want_samples=True)["samples"]
+                row = cached[k - first].clone()
+                row[torch.as_tensor(taken, device=row.device)] = float("inf")
+                i = int(torch.nonzero(row == row.min())[0, 0])
+            taken.append(i)
+            picks.append(i)
+    rows = Ct[torch.as_tensor(picks, device=Ct.device)].cpu().numpy()
+    t5 = time.perf_counter()
+    # host-clock split of the step, on the copy (scripts/paths_probe.py reports it)
+    opt.thompson_times = {"candidates_s": t1 - t0, "sample_s": t4 - t1, "dedupe_s": t5 - t4, "draws_s": t2 - t1,
+                          "prepare_s": t3 - t2, "eval_s": t4 - t3}
+    opt.thompson_collisions = r - len(set(argmin.tolist()))     # draws that did not keep their own argmin
+    if opt.trace is not None:
+        rec = {"thompson": True, "ts_sampler": "paths", "theta": (est.amp, est.length_scale.copy(), est.noise),
+               "omega": omega, "phase": phase, "w": w, "eps": eps, "picks": list(picks)}
+        if cand_seed is not None:
+            rec["cand_seed"] = cand_seed
+        else:
+            rec["cand"] = np.array(C)
+        opt.trace.append(rec)
+    return [list(x) for x in opt.space.inverse_transform(rows)]
+
+
 def _thompson_step(opt, r):
     """``r`` points from one Thompson step on the newest model of ``opt``."""
     import torch
 
-    n_ts = int(opt.acq_optimizer_kwargs.get("n_ts_points", 2048))
-    if n_ts > _lib.MPO_JOINT_MAX:
-        raise ValueError(f"n_ts_points = {n_ts} exceeds the joint posterior's {_lib.MPO_JOINT_MAX} points")
-    if r > n_ts:
-        raise ValueError(f"a Thompson batch of {r} points needs at least as many candidates, n_ts_points = {n_ts}")
+    sampler, n_ts, n_feat = thompson_config(opt.acq_optimizer_kwargs, opt.n_points, r)
+    if sampler == "paths":
+        return _thompson_paths_step(opt, r, n_ts, n_feat)
     est = opt.models[-1]
     t0 = time.perf_counter()
     cand_seed = None
@@ -502,7 +621,15 @@ class Optimizer:
     skopt: one fit, one joint draw of n posterior samples over
     ``acq_optimizer_kwargs["n_ts_points"]`` (2048, at most 4096) candidates
     (``mpo_gp_sample``), each point the argmin of its sample among the candidates no earlier
-    draw took -- no lie, no refit, no polish, no gp_hedge update for the batch."""
+    draw took -- no lie, no refit, no polish, no gp_hedge update for the batch.
+
+    ``acq_optimizer_kwargs["ts_sampler"]`` ("joint" | "paths", an addition of this build):
+    how a Thompson batch draws.  "joint" is the default, the draw above.  "paths" departs
+    further: pathwise posterior samples (``mpo_gp_paths_prepare`` / ``mpo_gp_paths_eval``) of
+    ``n_ts_features`` (2048, at most 4096) random Fourier features, evaluated at ALL
+    ``n_ts_points`` candidates (default ``n_points``, no 4096 cap), at most 1024 points per
+    batch.  The conditioning on the data is exact, the Matern prior is approximated: not
+    exact Thompson sampling, and nothing is known about its effect on search quality."""
 
     def __init__(self, dimensions, base_estimator="gp", n_random_starts=None, n_initial_points=10,
                  initial_point_generator="random", acq_func="gp_hedge", acq_optimizer="auto",
@@ -598,12 +725,7 @@ class Optimizer:
             raise ValueError(f"strategy {strategy!r}")
         if strategy == "thompson" and self.base_estimator_ == "gp":
             # refused here, before the copy's fit (_thompson_step checks again)
-            n_ts = self.acq_optimizer_kwargs.get("n_ts_points", 2048)
-            if n_ts > _lib.MPO_JOINT_MAX:
-                raise ValueError(f"n_ts_points = {n_ts} exceeds the joint posterior's {_lib.MPO_JOINT_MAX} points")
-            if n_points - max(self._n_initial_points, 0) > n_ts:
-                raise ValueError(f"a Thompson batch of {n_points} points needs at least as many candidates, "
-                                 f"n_ts_points = {n_ts}")
+            thompson_config(self.acq_optimizer_kwargs, self.n_points, n_points - max(self._n_initial_points, 0))
         if (n_points, strategy) in self.cache_:
             return self.cache_[(n_points, strategy)]
         if self.base_estimator_ == "gp" and self._n_initial_points - n_points <= 0:

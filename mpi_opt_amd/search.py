@@ -115,6 +115,11 @@ def make_parser():
                         "semantics) or thompson (NOT the reference's semantics: one fit per batch, one joint "
                         "draw of the posterior over n_ts_points candidates per point, each point the argmin of "
                         "its draw; no lies, no refits, no polish)")
+    p.add_argument("--thompson-sampler", default="joint", choices=["joint", "paths"], dest="thompson_sampler",
+                   help="how a thompson batch draws its samples: joint (the exact joint posterior over "
+                        "n_ts_points <= 4096 candidates) or paths (pathwise conditioning over all "
+                        "--ei-candidates: the conditioning on the data is exact, the Matern prior is a "
+                        "random-Fourier-feature APPROXIMATION; nothing is known about its effect on search quality)")
     return p
 
 
@@ -244,6 +249,9 @@ def run_search(args, x=None, y=None, log=print, progress=None, on_population=Non
         opt_kw["batch_strategy"] = args.batch_strategy    # Thompson ask batches (not skopt's semantics)
     if args.candidate_source != "host":
         opt_kw["candidates"] = args.candidate_source      # device-drawn candidates (not skopt's stream)
+    if args.thompson_sampler != "joint":
+        # pathwise Thompson draws over all --ei-candidates (a random-feature prior; not skopt's semantics)
+        opt_kw["acq_optimizer_kwargs"]["ts_sampler"] = args.thompson_sampler
     if chains is not None:
         opt_kw["chain_executor"] = chains                 # ask batches run concurrently (mpi_opt_amd.chains)
     if dist is not None:
