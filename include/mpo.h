@@ -394,6 +394,34 @@ int mpo_gp_paths_eval(const MpoGpModel* model, const MpoGpPaths* paths,
                       double* samples /*[n_draws][m] or NULL*/, int64_t* argmin /*[n_draws] or NULL*/,
                       double* minval /*[n_draws] or NULL*/, void* ws, size_t ws_bytes, void* stream);
 
+/* Value and gradient of draw[b] at the point x[b] (transformed space), b < batch: the
+ * objective of a continuous minimisation of a sample path.  With a_j = omega_j . c + phase_j,
+ * D_i = c - xs_i, k_i = sqrt(5) |D_i|:
+ *   f   = y_mean + y_std (sum_j cos(a_j) coef[j][r] + sum_i amp (1 + k_i + k_i^2/3) e^-k_i coef[Fp+i][r])
+ *   g_k = y_std / ls_k (- sum_j sin(a_j) coef[j][r] omega_jk
+ *                       - sum_i amp (5/3)(1 + k_i) e^-k_i coef[Fp+i][r] D_ik)
+ * ((dMatern/dr) / r: no division by r, an observation at x adds exactly 0).  One workgroup
+ * per run; every sum in a fixed order that depends on (F, n) alone: a run's f and g are the
+ * same bits whatever the batch, its order or the other runs in it.  Reads the model's plain
+ * xs and ls and the paths' omega, phase and coef only.
+ * MPO_EINVAL: a null pointer, batch outside [1, MPO_PATHS_GRAD_BMAX], a malformed model or
+ * paths struct, paths of another model shape; all checked on the host before any launch.  A
+ * draw[b] outside [0, s) cannot be seen from the host: that run's f and g are NaN, and
+ * nothing out of range is read.  Only enqueues work: no allocation, no host
+ * synchronisation, no atomics, capturable in a graph.
+ * NOT the reference's semantics (see above). */
+#define MPO_PATHS_GRAD_BMAX 8192
+int mpo_gp_paths_grad(const MpoGpModel* model, const MpoGpPaths* paths,
+                      const double* x /*[batch][d]*/, const int32_t* draw /*[batch]*/, int batch,
+                      double* f /*[batch]*/, double* g /*[batch][d]*/, void* stream);
+
+/* mpo_gp_paths_grad with x, draw, f, g in pinned (hipHostMalloc / registered) host memory,
+ * read and written by the kernel in place, then a synchronisation of `stream`.  MPO_EINVAL
+ * also if a buffer is not pinned host memory or a draw lies outside [0, s) (checked on the
+ * host here). */
+int mpo_gp_paths_grad_host(const MpoGpModel* model, const MpoGpPaths* paths, const double* x_host,
+                           const int32_t* draw_host, int batch, double* f_host, double* g_host, void* stream);
+
 /* ------------------------------------------------------------------------
  * Acquisition candidates drawn on the device (opt-in: Optimizer(candidates="device")).
  * skopt draws the n_points candidates of every ask on the host, column by column from
@@ -501,6 +529,15 @@ int mpo_gp_polish_host(const MpoGpModel* model, const double* starts, const int3
                        const double* bounds, const MpoLbfgsbOptions* opts, double y_opt, double xi, double kappa,
                        double* x_host, int32_t* acq_host, double* f_host, double* g_host, double* x_out,
                        double* f_out, int32_t* stats, int32_t* rounds, void* stream);
+
+/* Each draw of a set of sample paths minimised from its own start (NOT the reference's
+ * semantics): L-BFGS-B from starts [nruns][d] on draw[r] of `paths` (mpo_gp_paths_grad_host
+ * rounds through the pinned x_host [nruns][d], draw_host [nruns], f_host [nruns], g_host
+ * [nruns][d]).  MPO_EINVAL also for a draw outside [0, s). */
+int mpo_gp_paths_polish_host(const MpoGpModel* model, const MpoGpPaths* paths, const double* starts,
+                             const int32_t* draw, int nruns, const double* bounds, const MpoLbfgsbOptions* opts,
+                             double* x_host, int32_t* draw_host, double* f_host, double* g_host, double* x_out,
+                             double* f_out, int32_t* stats, int32_t* rounds, void* stream);
 
 /* ------------------------------------------------------------------------
  * Population training of ragged MNIST-CNN trials.

@@ -21,6 +21,7 @@ MPO_JOINT_MAX = 4096
 MPO_JOINT_SMAX = 1048560
 MPO_PATHS_FMAX = 4096
 MPO_PATHS_SMAX = 1024
+MPO_PATHS_GRAD_BMAX = 8192
 ACQ_FLAGS = {"EI": MPO_ACQ_EI, "PI": MPO_ACQ_PI, "LCB": MPO_ACQ_LCB}
 # MpoCnnSpec.options: option3's --loss / --optimizer (include/mpo.h MPO_LOSS_* | MPO_OPT_*)
 LOSS_CODES = {"binary_crossentropy": 0x0, "categorical_crossentropy": 0x1}
@@ -129,6 +130,8 @@ SIGNATURES = {
     "mpo_gp_paths_eval_ws_bytes": (_SZ, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpPaths), _I64, _I]),
     "mpo_gp_paths_eval": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpPaths), _P, _I64, _I, _I, _P, _P, _P,
                                _P, _SZ, _P]),
+    "mpo_gp_paths_grad": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpPaths), _P, _P, _I, _P, _P, _P]),
+    "mpo_gp_paths_grad_host": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpPaths), _P, _P, _I, _P, _P, _P]),
     "mpo_space_sample": (_I, [ctypes.POINTER(MpoDimDesc), _I, _I, ctypes.c_uint64, _I64, _I64, _P, _P]),
     "mpo_lbfgsb_batched": (_I, [_I, _I, _P, _P, ctypes.POINTER(MpoLbfgsbOptions), FG_BATCH_FN, _P, _P, _P, _P,
                                 _P]),
@@ -139,6 +142,8 @@ SIGNATURES = {
                                  _SZ, _P, _P, _P, _P, _P, _P]),
     "mpo_gp_polish_host": (_I, [ctypes.POINTER(MpoGpModel), _P, _P, _I, _P, ctypes.POINTER(MpoLbfgsbOptions), _D,
                                 _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mpo_gp_paths_polish_host": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpPaths), _P, _P, _I, _P,
+                                      ctypes.POINTER(MpoLbfgsbOptions), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mpo_pop_create": (_I, [ctypes.POINTER(MpoCnnSpec), _I, _I, ctypes.POINTER(ctypes.c_void_p)]),
     "mpo_pop_destroy": (_I, [_P]),
     "mpo_pop_sizes": (_I, [_P, ctypes.POINTER(MpoPopSizes)]),

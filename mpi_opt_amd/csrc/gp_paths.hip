@@ -14,6 +14,8 @@
 //   paths_eval_kernel    f_r(x) = y_mean + y_std (A(x) coef[:, r]),  A = [phi | amp Matern52(|c - xs|)],
 //                        the optional sample rows and the per-workgroup (min, index) of every draw
 //   paths_argmin_kernel  the workgroups' partials of a draw folded in order
+//   paths_grad_kernel    f_r(x) and its gradient at one point per workgroup (mpo_gp_paths_grad: the
+//                        objective of a continuous minimisation of a draw; no MFMA, latency-bound)
 // Fp = F rounded up to 16, Kp = Fp + np16 rounded up to 64 (the K panel), sp = s rounded up
 // to 16, plus 16 (a draw tile that starts at any first_draw stays inside the row).  Only the
 // plain W, xs, alpha and ls of the model are read, never wfrag: the same kernels serve a
@@ -285,6 +287,97 @@ __global__ void paths_argmin_kernel(const double* __restrict__ part_val, const l
     if (minval) minval[r] = bv;
 }
 
+// ---- value and gradient at a point ---------------------------------------------------------
+
+// Workgroup b: f and g of draw[b] at x[b].  The Fp + n terms (features, then observations)
+// go to thread tid, tid + 256, ..; a thread adds its terms' shares of f and of the gradient
+// IN THE SCALED SPACE (d / dc) into registers, DP a template parameter so that no private
+// array is indexed at run time.  The partials fold through a fixed butterfly in the wave,
+// then the four waves in order through the LDS; y_std and 1 / ls come once, at the end.
+// The order depends on (Fp, n) alone: a run's f and g are the same bits in any batch.
+//   feature j      a = omega_j . c + phase_j (the sum of paths_phi_kernel):
+//                  f += cos(a) coef_j,  dc += -sin(a) coef_j omega_j
+//   observation i  D = c - xs_i, k = sqrt(5) |D|:
+//                  f += amp (1 + k + k^2/3) e^-k coef_i,  dc += -amp (5/3)(1 + k) e^-k coef_i D
+// (dMatern/dr) / r has no division by r: an observation at the point itself adds exactly 0.
+// A draw outside [0, s) gives NaN and reads nothing.
+template <int DP>
+__global__ __launch_bounds__(256) void paths_grad_kernel(
+    const double* __restrict__ x, const int32_t* __restrict__ draw, int d, const double* __restrict__ ls,
+    const double* __restrict__ xs, int n, double amp, const double* __restrict__ om_p, const double* __restrict__ ph_p,
+    int Fp, const double* __restrict__ coef, int sp, int s, double y_mean, double y_std, double* __restrict__ f,
+    double* __restrict__ g) {
+    __shared__ double cs[DP];
+    __shared__ double part[4][DP + 1];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.x;
+    const int r = draw[b];
+    if (r < 0 || r >= s) {   // uniform over the workgroup
+        if (tid == 0) f[b] = NAN;
+        if (tid < d) g[(size_t)b * d + tid] = NAN;
+        return;
+    }
+    if (tid < DP) cs[tid] = tid < d ? x[(size_t)b * d + tid] / ls[tid] : 0.0;
+    __syncthreads();
+
+    double af = 0.0, ag[DP];
+#pragma unroll
+    for (int c = 0; c < DP; ++c) ag[c] = 0.0;
+    const double* cf = coef + r;
+    const int terms = Fp + n;
+    for (int t = tid; t < terms; t += 256) {
+        if (t < Fp) {
+            const double* om = om_p + (size_t)t * DP;
+            double w[DP];
+            double a = ph_p[t];
+#pragma unroll
+            for (int c = 0; c < DP; ++c) {
+                w[c] = om[c];
+                a = fma(w[c], cs[c], a);
+            }
+            const double cj = cf[(size_t)t * sp];
+            af = fma(cos(a), cj, af);
+            const double sj = -sin(a) * cj;
+#pragma unroll
+            for (int c = 0; c < DP; ++c) ag[c] = fma(sj, w[c], ag[c]);
+        } else {
+            const double* xo = xs + (size_t)(t - Fp) * DP;
+            double dl[DP];
+            double r2 = 0.0;
+#pragma unroll
+            for (int c = 0; c < DP; ++c) {
+                dl[c] = cs[c] - xo[c];
+                r2 += dl[c] * dl[c];
+            }
+            const double rr = sqrt(r2);
+            const double ci = cf[(size_t)t * sp];
+            af = fma(matern52(rr, amp), ci, af);
+            const double k = rr * mpo::kSqrt5;
+            const double gi = -(amp * ((5.0 / 3.0) * (1.0 + k) * exp(-k))) * ci;
+#pragma unroll
+            for (int c = 0; c < DP; ++c) ag[c] = fma(gi, dl[c], ag[c]);
+        }
+    }
+
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        af += __shfl_xor(af, off);
+#pragma unroll
+        for (int c = 0; c < DP; ++c) ag[c] += __shfl_xor(ag[c], off);
+    }
+    if (lane == 0) {
+        part[wave][DP] = af;
+#pragma unroll
+        for (int c = 0; c < DP; ++c) part[wave][c] = ag[c];
+    }
+    __syncthreads();
+    if (tid <= DP) {
+        const double v = ((part[0][tid] + part[1][tid]) + part[2][tid]) + part[3][tid];
+        if (tid == DP) f[b] = y_mean + y_std * v;
+        else if (tid < d) g[(size_t)b * d + tid] = y_std * v / ls[tid];
+    }
+}
+
 // ---- host ----------------------------------------------------------------------------------
 
 struct PathsWs {
@@ -342,6 +435,19 @@ int eval_grid_x(int64_t m, int n_draws) {
 // sized for the uncapped grid, whatever the knob says
 inline size_t eval_parts(int64_t m, int n_draws) {
     return (size_t)n_draws * (size_t)std::min<long long>(eval_tiles(m), kGridCap);
+}
+
+// the instance of a model's padded width (the widths of the scoring kernels); null otherwise
+using GradKernel = decltype(&paths_grad_kernel<4>);
+GradKernel pick_grad_kernel(int dp) {
+    switch (dp) {
+        case 4: return paths_grad_kernel<4>;
+        case 8: return paths_grad_kernel<8>;
+        case 12: return paths_grad_kernel<12>;
+        case 16: return paths_grad_kernel<16>;
+        case 32: return paths_grad_kernel<32>;
+        default: return nullptr;
+    }
 }
 
 }  // namespace
@@ -455,6 +561,61 @@ int mpo_gp_paths_eval(const MpoGpModel* model, const MpoGpPaths* paths, const do
                            n_draws, gx, reinterpret_cast<long long*>(argmin), minval);
         MPO_LAUNCH_CHECK();
     }
+    return MPO_OK;
+    MPO_GUARD_END
+}
+
+// the checks of mpo_gp_paths_grad and its _host form, all on the host
+static int paths_grad_check(const char* who, const MpoGpModel* model, const MpoGpPaths* paths, const void* x,
+                            const void* draw, int batch, const void* f, const void* g) {
+    MPO_CHECK_ARG(model && paths && x && draw && f && g, "%s: null pointer", who);
+    MPO_CHECK_ARG(batch >= 1 && batch <= MPO_PATHS_GRAD_BMAX, "%s: batch=%d outside [1, %d]", who, batch,
+                  MPO_PATHS_GRAD_BMAX);
+    MPO_CHECK_ARG(model_ok(model) && model->n <= mpo::kMaxObs && pick_grad_kernel(model->dp),
+                  "%s: malformed model n=%d d=%d dp=%d np16=%d", who, model->n, model->d, model->dp, model->np16);
+    MPO_CHECK_ARG(paths_ok(paths, model), "%s: malformed paths F=%d s=%d n=%d dp=%d Fp=%d Kp=%d sp=%d", who, paths->F,
+                  paths->s, paths->n, paths->dp, paths->Fp, paths->Kp, paths->sp);
+    return MPO_OK;
+}
+
+int mpo_gp_paths_grad(const MpoGpModel* model, const MpoGpPaths* paths, const double* x, const int32_t* draw, int batch,
+                      double* f, double* g, void* stream) {
+    MPO_GUARD_BEGIN
+    if (const int rc = paths_grad_check("mpo_gp_paths_grad", model, paths, x, draw, batch, f, g)) return rc;
+    hipLaunchKernelGGL(pick_grad_kernel(model->dp), dim3(batch), dim3(256), 0, static_cast<hipStream_t>(stream), x,
+                       draw, model->d, model->ls, model->xs, model->n, model->amp, paths->omega, paths->phase,
+                       paths->Fp, paths->coef, paths->sp, paths->s, model->y_mean, model->y_std, f, g);
+    MPO_LAUNCH_CHECK();
+    return MPO_OK;
+    MPO_GUARD_END
+}
+
+int mpo_gp_paths_grad_host(const MpoGpModel* model, const MpoGpPaths* paths, const double* x_host,
+                           const int32_t* draw_host, int batch, double* f_host, double* g_host, void* stream) {
+    MPO_GUARD_BEGIN
+    const char* who = "mpo_gp_paths_grad_host";
+    if (const int rc = paths_grad_check(who, model, paths, x_host, draw_host, batch, f_host, g_host)) return rc;
+    mpo::StreamDeviceScope on_device(static_cast<hipStream_t>(stream));
+    auto dev_view = [](const void* h) -> void* {
+        hipPointerAttribute_t at{};
+        if (hipPointerGetAttributes(&at, h) != hipSuccess || at.type != hipMemoryTypeHost || !at.devicePointer) {
+            (void)hipGetLastError();
+            return nullptr;
+        }
+        return at.devicePointer;
+    };
+    void* xd = dev_view(x_host);
+    void* dd = dev_view(draw_host);
+    void* fd = dev_view(f_host);
+    void* gd = dev_view(g_host);
+    MPO_CHECK_ARG(xd && dd && fd && gd, "%s: buffers must be pinned host memory", who);
+    for (int b = 0; b < batch; ++b)
+        MPO_CHECK_ARG(draw_host[b] >= 0 && draw_host[b] < paths->s, "%s: draw[%d]=%d outside [0, %d)", who, b,
+                      draw_host[b], paths->s);
+    const int rc = mpo_gp_paths_grad(model, paths, static_cast<const double*>(xd), static_cast<const int32_t*>(dd),
+                                     batch, static_cast<double*>(fd), static_cast<double*>(gd), stream);
+    if (rc != MPO_OK) return rc;
+    MPO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     return MPO_OK;
     MPO_GUARD_END
 }

@@ -1320,4 +1320,28 @@ int mpo_gp_polish_host(const MpoGpModel* model, const double* starts, const int3
     MPO_GUARD_END
 }
 
+int mpo_gp_paths_polish_host(const MpoGpModel* model, const MpoGpPaths* paths, const double* starts,
+                             const int32_t* draw, int nruns, const double* bounds, const MpoLbfgsbOptions* opts,
+                             double* x_host, int32_t* draw_host, double* f_host, double* g_host, double* x_out,
+                             double* f_out, int32_t* stats, int32_t* rounds, void* stream) {
+    MPO_GUARD_BEGIN
+    MPO_CHECK_ARG(model && paths && draw && x_host && draw_host && f_host && g_host && x_out && f_out,
+                  "mpo_gp_paths_polish_host: null pointer");
+    const int d = model->d;
+    MPO_CHECK_ARG(options_ok(d, nruns, starts, bounds, opts), "mpo_gp_paths_polish_host: bad options / bounds");
+    MPO_CHECK_ARG(nruns <= MPO_PATHS_GRAD_BMAX, "mpo_gp_paths_polish_host: nruns=%d exceeds %d", nruns,
+                  MPO_PATHS_GRAD_BMAX);
+    auto eval = [&](int b, const double* Xp, const int32_t* ids, double* f, double* g) -> int {
+        std::memcpy(x_host, Xp, sizeof(double) * (size_t)b * d);
+        for (int i = 0; i < b; ++i) draw_host[i] = draw[ids[i]];
+        const int rc = mpo_gp_paths_grad_host(model, paths, x_host, draw_host, b, f_host, g_host, stream);
+        if (rc != MPO_OK) return rc;
+        std::memcpy(f, f_host, sizeof(double) * b);
+        std::memcpy(g, g_host, sizeof(double) * (size_t)b * d);
+        return 0;
+    };
+    return drive(d, nruns, starts, bounds, to_options(opts), eval, x_out, f_out, stats, rounds);
+    MPO_GUARD_END
+}
+
 }  // extern "C"

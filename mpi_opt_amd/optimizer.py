@@ -125,7 +125,9 @@ class GPModel:
         number of times.  Pathwise conditioning (``mpo_gp_paths_prepare`` / ``_eval``): the
         conditioning on the data is exact, the Matern-5/2 prior is approximated by
         ``n_features`` random Fourier features drawn by
-        ``draw_paths(RandomState(random_state), ...)``."""
+        ``draw_paths(RandomState(random_state), ...)``.  A sample is differentiable:
+        ``paths.grad(X, draws)`` gives values and gradients (``mpo_gp_paths_grad``) and
+        ``paths.minimize(starts, draws, bounds)`` minimises each sample from its own start."""
         from .paths import check_sizes, draw_paths
 
         n_samples, n_features = int(n_samples), int(n_features)
@@ -137,7 +139,20 @@ class GPModel:
             X = np.atleast_2d(np.asarray(X, dtype=float))
             return dp.eval(X, want_samples=True)["samples"].cpu().numpy().T
 
+        def grad(X, draws):
+            """numpy ``(f (B,), g (B, d))`` of sample ``draws[b]`` at the row ``X[b]``."""
+            f, g = dp.grad(np.atleast_2d(np.asarray(X, dtype=float)), draws)
+            return f.cpu().numpy(), g.cpu().numpy()
+
+        def minimize(starts, draws, bounds):
+            """Sample ``draws[b]`` minimised from ``starts[b]`` within ``bounds`` (d, 2) by
+            L-BFGS-B (20 iterations, skopt's polish settings): numpy ``(x (B, d), f (B,))``."""
+            x, f, _, _ = dp.polish(np.atleast_2d(np.asarray(starts, dtype=float)), draws, bounds)
+            return x, f
+
         paths.device_paths = dp
+        paths.grad = grad
+        paths.minimize = minimize
         return paths
 
 
@@ -457,10 +472,18 @@ def thompson_config(kwargs, n_points, r):
     """``(ts_sampler, n_ts_points, n_ts_features)`` of a Thompson step of ``r`` points under
     ``acq_optimizer_kwargs`` (``n_points``: the optimizer's candidate count, the default of
     ``n_ts_points`` for the "paths" sampler), or the ``ValueError`` that refuses it.  Host
-    arithmetic only: ``ask`` calls it before any fit, ``_thompson_step`` again."""
+    arithmetic only: ``ask`` calls it before any fit, ``_thompson_step`` again.  Also refuses
+    an ``acq_optimizer_kwargs["ts_polish"]`` that is not a bool, or that is set under the
+    "joint" sampler."""
     sampler = kwargs.get("ts_sampler", "joint")
     if sampler not in TS_SAMPLERS:
         raise ValueError(f"ts_sampler {sampler!r}: one of {TS_SAMPLERS}")
+    polish = kwargs.get("ts_polish", False)
+    if not isinstance(polish, (bool, np.bool_)):
+        raise ValueError(f"ts_polish {polish!r}: a bool")
+    if polish and sampler == "joint":
+        raise ValueError('ts_polish needs ts_sampler = "paths": a joint draw is a vector over the candidates, '
+                         "not a function that could be minimised")
     n_feat = int(kwargs.get("n_ts_features", 2048))
     if sampler == "joint":
         n_ts = int(kwargs.get("n_ts_points", 2048))
@@ -475,6 +498,21 @@ def thompson_config(kwargs, n_points, r):
     if r > n_ts:
         raise ValueError(f"a Thompson batch of {r} points needs at least as many candidates, n_ts_points = {n_ts}")
     return sampler, n_ts, n_feat
+
+
+def thompson_polish_accept(polished, fallback):
+    """The points of a polished Thompson batch, in draw order: draw k keeps ``polished[k]``
+    (its minimiser after the inverse transform) unless that equals a point already accepted
+    in this batch; then it falls back to ``fallback[k]``, its unpolished candidate.
+    Returns ``(points, kept)``, ``kept[k]`` true where the polished point stayed."""
+    seen, points, kept = set(), [], []
+    for p, c in zip(polished, fallback):
+        keep = tuple(p) not in seen
+        x = list(p if keep else c)
+        seen.add(tuple(x))
+        points.append(x)
+        kept.append(keep)
+    return points, kept
 
 
 def _thompson_paths_step(opt, r, n_ts, n_feat):
@@ -532,8 +570,22 @@ def _thompson_paths_step(opt, r, n_ts, n_feat):
     rows = Ct[torch.as_tensor(picks, device=Ct.device)].cpu().numpy()
     t5 = time.perf_counter()
     # host-clock split of the step, on the copy (scripts/paths_probe.py reports it)
+    points = [list(x) for x in opt.space.inverse_transform(rows)]
+    polish = None
+    opt.thompson_polished, opt.thompson_polish_rounds = 0, 0
+    if opt.acq_optimizer_kwargs.get("ts_polish", False):
+        # each draw minimised from its own pick (mpo_gp_paths_polish_host); no RandomState draw
+        draws = np.arange(r, dtype=np.int32)
+        x, f, stats, rounds = paths.polish(rows, draws, opt.space.transformed_bounds)
+        polished = opt.space.inverse_transform(np.clip(x, 0.0, 1.0))
+        points, kept = thompson_polish_accept([list(p) for p in polished], points)
+        opt.thompson_polished, opt.thompson_polish_rounds = int(sum(kept)), rounds
+        if opt.trace is not None:
+            polish = {"x": x, "f": f, "f_start": paths.grad(rows, draws)[0].cpu().numpy(), "stats": stats,
+                      "kept": list(kept)}
+    t6 = time.perf_counter()
     opt.thompson_times = {"candidates_s": t1 - t0, "sample_s": t4 - t1, "dedupe_s": t5 - t4, "draws_s": t2 - t1,
-                          "prepare_s": t3 - t2, "eval_s": t4 - t3}
+                          "prepare_s": t3 - t2, "eval_s": t4 - t3, "polish_s": t6 - t5}
     opt.thompson_collisions = r - len(set(argmin.tolist()))     # draws that did not keep their own argmin
     if opt.trace is not None:
         rec = {"thompson": True, "ts_sampler": "paths", "theta": (est.amp, est.length_scale.copy(), est.noise),
@@ -542,8 +594,10 @@ def _thompson_paths_step(opt, r, n_ts, n_feat):
             rec["cand_seed"] = cand_seed
         else:
             rec["cand"] = np.array(C)
+        if polish is not None:
+            rec["polish"] = polish
         opt.trace.append(rec)
-    return [list(x) for x in opt.space.inverse_transform(rows)]
+    return points
 
 
 def _thompson_step(opt, r):
@@ -629,7 +683,17 @@ class Optimizer:
     ``n_ts_features`` (2048, at most 4096) random Fourier features, evaluated at ALL
     ``n_ts_points`` candidates (default ``n_points``, no 4096 cap), at most 1024 points per
     batch.  The conditioning on the data is exact, the Matern prior is approximated: not
-    exact Thompson sampling, and nothing is known about its effect on search quality."""
+    exact Thompson sampling, and nothing is known about its effect on search quality.
+
+    ``acq_optimizer_kwargs["ts_polish"]`` (bool, default ``False``, an addition of this build;
+    "paths" sampler only, refused under "joint"): after the batch above is picked, each draw
+    is minimised continuously from its own picked candidate -- L-BFGS-B with the settings of
+    skopt's acquisition polish (20 iterations) on the draw's closed-form value and gradient
+    (``mpo_gp_paths_grad``), all draws in lockstep (``mpo_gp_paths_polish_host``).  A draw
+    keeps its polished point unless, after the inverse transform, it equals a point already
+    accepted in the batch; then it keeps its candidate (``thompson_polish_accept``).  No extra
+    RandomState draw.  NOT the reference's semantics, and nothing is known about its effect
+    on search quality."""
 
     def __init__(self, dimensions, base_estimator="gp", n_random_starts=None, n_initial_points=10,
                  initial_point_generator="random", acq_func="gp_hedge", acq_optimizer="auto",

@@ -7,6 +7,11 @@ The conditioning on the data is exact; the Matern-5/2 prior is APPROXIMATED by `
 random features.  NOT the reference's semantics (skopt has no such sampler): opt-in,
 behind ``acq_optimizer_kwargs["ts_sampler"] = "paths"`` and ``GPModel.sample_paths``.
 
+A draw is differentiable in closed form: :meth:`DevicePaths.grad` (``mpo_gp_paths_grad``)
+gives its value and gradient at a point, :meth:`DevicePaths.polish`
+(``mpo_gp_paths_polish_host``) minimises each draw from its own start; behind
+``acq_optimizer_kwargs["ts_polish"]``, off by default.
+
 :func:`draw_paths` is the one place the law of the random inputs lives on the host.
 """
 from __future__ import annotations
@@ -18,6 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr
+from .gp_fit import FMIN_FTOL
 
 #: one ``want_samples=True`` evaluation may hold this many bytes of sample rows
 SAMPLE_ROWS_MAX_BYTES = 256 << 20
@@ -109,3 +115,70 @@ class DevicePaths:
                                       ptr(samples), ptr(argmin), ptr(minval), ptr(self._eval_ws),
                                       self._eval_ws.numel(), _lib.stream_handle(dev)), "mpo_gp_paths_eval")
         return {"samples": samples, "argmin": argmin, "minval": minval}
+
+    def _check_draws(self, draws, B):
+        dr = np.ascontiguousarray(np.asarray(draws, dtype=np.int32).reshape(-1))
+        if dr.shape != (B,):
+            raise ValueError(f"one draw per point: {B} points, {dr.shape[0]} draws")
+        if not 1 <= B <= _lib.MPO_PATHS_GRAD_BMAX:
+            raise ValueError(f"one call takes 1 .. {_lib.MPO_PATHS_GRAD_BMAX} points (MPO_PATHS_GRAD_BMAX), got {B}")
+        return dr
+
+    def grad(self, X, draws):
+        """``mpo_gp_paths_grad``: the value ``f`` (B,) and the gradient ``g`` (B, d) of draw
+        ``draws[b]`` at the row ``X[b]`` (transformed space), device tensors.  A run's bits do
+        not depend on the batch around it; a draw outside ``[0, s)`` gives NaN."""
+        gp = self.gp
+        x = gp.as_candidates(X)
+        B = x.shape[0]
+        dr = torch.from_numpy(self._check_draws(draws, B)).to(gp.device)
+        dev = gp.device
+        f = torch.empty(B, dtype=torch.float64, device=dev)
+        g = torch.empty(B, gp.d, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            check(lib().mpo_gp_paths_grad(ctypes.byref(gp.model), ctypes.byref(self.paths), ptr(x), ptr(dr), B, ptr(f),
+                                          ptr(g), _lib.stream_handle(dev)), "mpo_gp_paths_grad")
+        return f, g
+
+    def _ensure_pg(self, B):
+        """Pinned host buffers of one polish round (x, draw ids, f, g) for B runs."""
+        if getattr(self, "_pg_cap", 0) < B:
+            cap = max(16, B)
+            d = self.gp.d
+            self._pg_bufs = (torch.empty(cap * d, dtype=torch.float64).pin_memory(),
+                             torch.empty(cap, dtype=torch.int32).pin_memory(),
+                             torch.empty(cap, dtype=torch.float64).pin_memory(),
+                             torch.empty(cap * d, dtype=torch.float64).pin_memory())
+            self._pg_ptrs = tuple(t.data_ptr() for t in self._pg_bufs)
+            self._pg_cap = cap
+
+    def polish(self, starts, draws, bounds, ftol=FMIN_FTOL, maxiter=20, gtol=1e-5, maxfun=15000):
+        """``mpo_gp_paths_polish_host``: L-BFGS-B (libmpo.so's host driver, the settings of
+        skopt's acquisition polish) from the row ``starts[r]`` (B, d) on draw ``draws[r]``,
+        within ``bounds`` (d, 2); one ``mpo_gp_paths_grad_host`` round per iteration of all
+        live runs.  Returns numpy ``(x (B, d), f (B,), stats (B, 4) = (nit, nfev, status, 0),
+        rounds)``; ``f[r]`` is ``grad``'s value at ``x[r]`` bit for bit.  As with scipy's
+        L-BFGS-B, a coordinate of ``x`` may pass its bound by one rounding error of the line
+        search's ``t + stp d`` (-8.7e-19 was seen at a lower bound 0): clip before use."""
+        gp = self.gp
+        starts = np.ascontiguousarray(np.asarray(starts, dtype=np.float64))
+        if starts.ndim != 2 or starts.shape[1] != gp.d:
+            raise ValueError(f"polish starts must be (B, {gp.d}), got {starts.shape}")
+        B, d = starts.shape
+        dr = self._check_draws(draws, B)
+        if dr.min() < 0 or dr.max() >= self.s:
+            raise ValueError(f"draws outside [0, {self.s})")
+        self._ensure_pg(B)
+        b = np.ascontiguousarray(np.asarray(bounds, dtype=np.float64).reshape(d, 2))
+        opts = _lib.MpoLbfgsbOptions(ftol, gtol, maxiter, maxfun, 10, 20)
+        x = np.empty((B, d))
+        f = np.empty(B)
+        stats = np.empty((B, 4), np.int32)
+        rounds = ctypes.c_int32(0)
+        xp, ip, fp, gp_ = self._pg_ptrs
+        with torch.cuda.device(gp.device):
+            check(lib().mpo_gp_paths_polish_host(ctypes.byref(gp.model), ctypes.byref(self.paths), starts.ctypes.data,
+                                                 dr.ctypes.data, B, b.ctypes.data, ctypes.byref(opts), xp, ip, fp, gp_,
+                                                 x.ctypes.data, f.ctypes.data, stats.ctypes.data, ctypes.byref(rounds),
+                                                 _lib.stream_handle(gp.device)), "mpo_gp_paths_polish_host")
+        return x, f, stats, int(rounds.value)

@@ -120,6 +120,11 @@ def make_parser():
                         "n_ts_points <= 4096 candidates) or paths (pathwise conditioning over all "
                         "--ei-candidates: the conditioning on the data is exact, the Matern prior is a "
                         "random-Fourier-feature APPROXIMATION; nothing is known about its effect on search quality)")
+    p.add_argument("--thompson-polish", action="store_true", dest="thompson_polish",
+                   help="with --batch-strategy thompson --thompson-sampler paths: minimise each sample path "
+                        "from its picked candidate by L-BFGS-B (20 iterations) instead of stopping at the "
+                        "candidate (NOT the reference's semantics; nothing is known about its effect on "
+                        "search quality)")
     return p
 
 
@@ -252,6 +257,8 @@ def run_search(args, x=None, y=None, log=print, progress=None, on_population=Non
     if args.thompson_sampler != "joint":
         # pathwise Thompson draws over all --ei-candidates (a random-feature prior; not skopt's semantics)
         opt_kw["acq_optimizer_kwargs"]["ts_sampler"] = args.thompson_sampler
+    if getattr(args, "thompson_polish", False):
+        opt_kw["acq_optimizer_kwargs"]["ts_polish"] = True    # each draw minimised from its pick
     if chains is not None:
         opt_kw["chain_executor"] = chains                 # ask batches run concurrently (mpi_opt_amd.chains)
     if dist is not None:
@@ -323,6 +330,10 @@ def main(argv=None):
         check_training_flags(args)
     except ValueError as e:
         print(f"error: {e}", file=sys.stderr)
+        return 2
+    if args.thompson_polish and (args.batch_strategy != "thompson" or args.thompson_sampler != "paths"):
+        print("error: --thompson-polish needs --batch-strategy thompson --thompson-sampler paths "
+              "(only a sample path is a function that can be minimised)", file=sys.stderr)
         return 2
     if args.example != "mnist":
         print(f"example {args.example!r}: its data ({'LCD jets' if args.example == 'topclass' else '3D GAN'}) "
