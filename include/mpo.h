@@ -247,6 +247,68 @@ int mpo_gp_acq_grad_host(const MpoGpModel* model, const double* x_host, int batc
                          double y_opt, double xi, double kappa, double* f_host, double* g_host, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Cost-aware acquisitions EIps / PIps (skopt acquisition.py: acq_func "EIps" / "PIps",
+ * reached from Coordinator.ask, coordinator.py:46-50, once tell receives (value, time)
+ * pairs).  Two prepared models over the SAME observations: fmodel on the objective, tmodel
+ * on log t.  With a(x) = -EI or -PI under fmodel (mpo_gp_acq_score's value, the sd <= 0 -> 0
+ * rule included) and (mu, s) = tmodel's posterior mean / std in the units of log t:
+ *   inv_t(x) = exp(-mu + s^2 / 2)      E[1/t] of a log-normal t, evaluated as
+ *                                      exp(fma(0.5 s, s, -mu)) with the device library's exp
+ *   v(x)     = a(x) inv_t(x)           the value that is minimised
+ *   grad v   = grad a inv_t + v (-grad mu + s grad s)
+ * MPO_EINVAL: a null or malformed model, fmodel->n != tmodel->n or another d.  All refusals
+ * are made on the host before any launch; the device forms only enqueue work: no
+ * allocation, no host synchronisation, no atomics.
+ * ---------------------------------------------------------------------- */
+
+/* Workspace bytes of mpo_gp_acq_ps_score: the larger of the two models' scoring workspaces
+ * (the passes run one after the other), 4 rows of m doubles and the finish pass's top-k
+ * lists.  0 for what that call refuses. */
+size_t mpo_gp_acq_ps_ws_bytes(const MpoGpModel* fmodel, const MpoGpModel* tmodel, int64_t m, int k);
+
+/* Score m candidates ([m][d] device): fmodel's scoring path (resident or streamed, as
+ * mpo_gp_score_path says) into workspace value rows, tmodel's into workspace mu / sd rows,
+ * then one elementwise finish pass:
+ *   vals[a*m + i]          v of acquisition a in {EI, PI} order (mpo_gp_acq_score's rows;
+ *                          rows of unset flags untouched)            ([2][m] or NULL)
+ *   inv_t[i]                                                           ([m] or NULL)
+ *   topk_idx/val[a*k + r]  the k smallest v of acquisition a by (value, index): lowest index
+ *                          on ties, -0.0 == 0.0; index -1 where m < k (NULL with k = 0)
+ * flags is a non-empty subset of MPO_ACQ_EI | MPO_ACQ_PI.  A candidate's outputs do not
+ * depend on m, on the grid or on the rows around it.  MPO_EINVAL also for m < 1, a flag
+ * outside EI | PI, k outside [0, MPO_TOPK_MAX], k > 0 without top-k outputs, k = 0 with
+ * neither vals nor inv_t, a workspace smaller than mpo_gp_acq_ps_ws_bytes. */
+int mpo_gp_acq_ps_score(const MpoGpModel* fmodel, const MpoGpModel* tmodel, const double* cand, int64_t m,
+                        double y_opt, double xi, unsigned flags, double* vals, double* inv_t, int k,
+                        int64_t* topk_idx, double* topk_val, void* ws, size_t ws_bytes, void* stream);
+
+/* The polish objective: f[b] = v and g[b][d] = grad v of acquisition acq[b] (device int32,
+ * MPO_ACQ_EI or MPO_ACQ_PI; any other code cannot be seen from the host and gives NaN) at
+ * the points x [batch][d] (device); parts (or NULL) [batch][4] = (a, inv_t, mu_t, s_t).  One
+ * launch, one workgroup per point: both posteriors and their gradients one model after the
+ * other in the same LDS, each by the sequence of mpo_gp_acq_grad's kernel in that kernel's
+ * summation order; 16 waves per point while 19 n doubles plus the static LDS fit the
+ * 160 KiB, 4 past it (mpo_gp_acq_ps_grad_path), every n <= 2048.  Every sum runs in a fixed
+ * order: a point's f and g are the same bits whatever the batch or its order.
+ * batch in [1, 65535]. */
+int mpo_gp_acq_ps_grad(const MpoGpModel* fmodel, const MpoGpModel* tmodel, const double* x, int batch,
+                       const int32_t* acq, double y_opt, double xi, double* f, double* g, double* parts,
+                       void* stream);
+
+/* Waves per point (16 or 4) of the kernel mpo_gp_acq_ps_grad launches for this pair, or
+ * negative (-MPO_EINVAL, -MPO_ENOTSUP) when it would be refused.  Needs a device, as
+ * mpo_gp_acq_grad_path does. */
+int mpo_gp_acq_ps_grad_path(const MpoGpModel* fmodel, const MpoGpModel* tmodel);
+
+/* One polish round from the host: mpo_gp_acq_ps_grad with x, acq, f, g (and parts, when
+ * given) in pinned host memory, read and written in place, then one synchronisation of
+ * `stream`.  MPO_EINVAL also if a buffer is not pinned or a code is neither EI nor PI
+ * (checked on the host here). */
+int mpo_gp_acq_ps_grad_host(const MpoGpModel* fmodel, const MpoGpModel* tmodel, const double* x_host, int batch,
+                            const int32_t* acq_host, double y_opt, double xi, double* f_host, double* g_host,
+                            double* parts_host, void* stream);
+
+/* ------------------------------------------------------------------------
  * The JOINT posterior of a prepared model over m query points (transformed space,
  * [m][d] device): what sklearn's GaussianProcessRegressor.predict(X, return_cov=True)
  * and sample_y(X, n_samples) give (_gpr.py:370-470, 472-507), for skopt's fitted GP
@@ -529,6 +591,15 @@ int mpo_gp_polish_host(const MpoGpModel* model, const double* starts, const int3
                        const double* bounds, const MpoLbfgsbOptions* opts, double y_opt, double xi, double kappa,
                        double* x_host, int32_t* acq_host, double* f_host, double* g_host, double* x_out,
                        double* f_out, int32_t* stats, int32_t* rounds, void* stream);
+
+/* mpo_gp_polish_host on the cost-aware objective: L-BFGS-B from starts [nruns][d] on
+ * acquisition acq[r] (MPO_ACQ_EI / MPO_ACQ_PI) per unit cost, one mpo_gp_acq_ps_grad_host
+ * round per iteration of all live runs through the same pinned buffers.  skopt's polish
+ * with acq_func "EIps" / "PIps". */
+int mpo_gp_polish_ps_host(const MpoGpModel* fmodel, const MpoGpModel* tmodel, const double* starts,
+                          const int32_t* acq, int nruns, const double* bounds, const MpoLbfgsbOptions* opts,
+                          double y_opt, double xi, double* x_host, int32_t* acq_host, double* f_host, double* g_host,
+                          double* x_out, double* f_out, int32_t* stats, int32_t* rounds, void* stream);
 
 /* Each draw of a set of sample paths minimised from its own start (NOT the reference's
  * semantics): L-BFGS-B from starts [nruns][d] on draw[r] of `paths` (mpo_gp_paths_grad_host

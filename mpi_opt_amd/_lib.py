@@ -121,6 +121,14 @@ SIGNATURES = {
     "mpo_gp_acq_grad": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _D, _D, _D, _P, _P, _P]),
     "mpo_gp_acq_grad_path": (_I, [ctypes.POINTER(MpoGpModel)]),
     "mpo_gp_acq_grad_host": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _D, _D, _D, _P, _P, _P]),
+    "mpo_gp_acq_ps_ws_bytes": (_SZ, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpModel), _I64, _I]),
+    "mpo_gp_acq_ps_score": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpModel), _P, _I64, _D, _D, _U, _P, _P,
+                                 _I, _P, _P, _P, _SZ, _P]),
+    "mpo_gp_acq_ps_grad": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpModel), _P, _I, _P, _D, _D, _P, _P, _P,
+                                _P]),
+    "mpo_gp_acq_ps_grad_path": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpModel)]),
+    "mpo_gp_acq_ps_grad_host": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpModel), _P, _I, _P, _D, _D, _P,
+                                     _P, _P, _P]),
     "mpo_gp_joint_ws_bytes": (_SZ, [ctypes.POINTER(MpoGpModel), _I, _I]),
     "mpo_gp_posterior_cov": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _P, _I, _P, _SZ, _P]),
     "mpo_gp_sample": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _I, _D, _P, _P, _P, _P, _SZ, _P]),
@@ -142,6 +150,8 @@ SIGNATURES = {
                                  _SZ, _P, _P, _P, _P, _P, _P]),
     "mpo_gp_polish_host": (_I, [ctypes.POINTER(MpoGpModel), _P, _P, _I, _P, ctypes.POINTER(MpoLbfgsbOptions), _D,
                                 _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mpo_gp_polish_ps_host": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpModel), _P, _P, _I, _P,
+                                   ctypes.POINTER(MpoLbfgsbOptions), _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mpo_gp_paths_polish_host": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpPaths), _P, _P, _I, _P,
                                       ctypes.POINTER(MpoLbfgsbOptions), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mpo_pop_create": (_I, [ctypes.POINTER(MpoCnnSpec), _I, _I, ctypes.POINTER(ctypes.c_void_p)]),

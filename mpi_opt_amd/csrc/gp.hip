@@ -29,6 +29,7 @@
 // ~1000x less rounding error (DESIGN.md "GP posterior formulation").
 
 #include "mpo_internal.h"
+#include "gp_acq_math.h"
 
 #include <algorithm>
 #include <cmath>
@@ -41,8 +42,10 @@ typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 using mpo::kSqrt5;
 using mpo::matern52;   // mpo_internal.h: shared with gp_joint.hip
-constexpr double kSqrt1_2 = 0.707106781186547524400844362104849039;
-constexpr double kSqrt2Pi = 2.506628274631000502415765284811045253;
+using mpo::ndtr;       // gp_acq_math.h: shared with gp_ps.hip
+using mpo::norm_pdf;
+using mpo::lex_less;
+using mpo::wave_lex_min;
 constexpr double kJitter = 1e-10;
   // sklearn GPR alpha default (_gpr.py:207)
 
@@ -109,90 +112,6 @@ constexpr double kR2Floor = 1e-300;
 __device__ __forceinline__ double matern52_unit(double r2) {
     const double k = sqrt_pos(r2) * kSqrt5;
     return fma(r2, 5.0 / 3.0, 1.0 + k) * exp_neg(k);
-}
-
-// scipy.special.ndtr, the kernel of scipy.stats.norm.cdf (skopt's EI / PI): cephes
-// ndtr.c's own algorithm -- erf as x T(x^2) / U(x^2) for |x| <= 1, erfc as
-// exp(-x^2) P(x) / Q(x) (1 <= x < 8) or R(x) / S(x) (x >= 8), Horner without FMA
-// contraction as the host build evaluates it -- instead of the device libm's
-// erf / erfc: with the same exp the results are scipy's bits (CPU check of these
-// constants: 98.5% of 300k points bit-exact, the rest within 4.4e-16 relative).  The
-// scoring pass times the same (1.40 vs 1.40 ms median, same box, profiles/r05/ei_ndtr_ab_ad.log).
-namespace cephes {
-__constant__ constexpr double kP[9] = {2.46196981473530512524E-10, 5.64189564831068821977E-1, 7.46321056442269912687E0,
-                                       4.86371970985681366614E1,   1.96520832956077098242E2, 5.26445194995477358631E2,
-                                       9.34528527171957607540E2,   1.02755188689515710272E3, 5.57535335369399327526E2};
-__constant__ constexpr double kQ[8] = {1.32281951154744992508E1, 8.67072140885989742329E1, 3.54937778887819891062E2,
-                                       9.75708501743205489753E2, 1.82390916687909736289E3, 2.24633760818710981792E3,
-                                       1.65666309194161350182E3, 5.57535340817727675546E2};
-__constant__ constexpr double kR[6] = {5.64189583547755073984E-1, 1.27536670759978104416E0, 5.01905042251180477414E0,
-                                       6.16021097993053585195E0,  7.40974269950448939160E0, 2.97886665372100240670E0};
-__constant__ constexpr double kS[6] = {2.26052863220117276590E0, 9.39603524938001434673E0, 1.20489539808096656605E1,
-                                       1.70814450747565897222E1, 9.60896809063285878198E0, 3.36907645100081516050E0};
-__constant__ constexpr double kT[5] = {9.60497373987051638749E0, 9.00260197203842689217E1, 2.23200534594684319226E3,
-                                       7.00332514112805075473E3, 5.55923013010394962768E4};
-__constant__ constexpr double kU[5] = {3.35617141647503099647E1, 5.21357949780152679795E2, 4.59432382970980127987E3,
-                                       2.26290000613890934246E4, 4.92673942608635921086E4};
-constexpr double kMaxLog = 7.09782712893383996843E2;
-
-template <int N>
-__device__ __forceinline__ double polevl(double x, const double (&c)[N]) {
-#pragma clang fp contract(off)
-    double y = c[0];
-#pragma unroll
-    for (int i = 1; i < N; ++i) y = y * x + c[i];
-    return y;
-}
-template <int N>   // leading coefficient 1
-__device__ __forceinline__ double p1evl(double x, const double (&c)[N]) {
-#pragma clang fp contract(off)
-    double y = x + c[0];
-#pragma unroll
-    for (int i = 1; i < N; ++i) y = y * x + c[i];
-    return y;
-}
-// erf for |x| <= 1
-__device__ __forceinline__ double erf_small(double x) {
-#pragma clang fp contract(off)
-    const double z = x * x;
-    return x * polevl(z, kT) / p1evl(z, kU);
-}
-// erfc for x >= 1
-__device__ __forceinline__ double erfc_large(double x) {
-#pragma clang fp contract(off)
-    const double z = -x * x;
-    if (z < -kMaxLog) return 0.0;
-    const double e = exp(z);
-    const double y = x < 8.0 ? (e * polevl(x, kP)) / p1evl(x, kQ) : (e * polevl(x, kR)) / p1evl(x, kS);
-    return y;
-}
-}  // namespace cephes
-
-__device__ __forceinline__ double ndtr(double a) {
-#pragma clang fp contract(off)
-    if (isnan(a)) return a;
-    const double x = a * kSqrt1_2;
-    const double z = fabs(x);
-    if (z < kSqrt1_2) return 0.5 + 0.5 * cephes::erf_small(x);
-    // z >= sqrt(1/2); cephes erfc(z) takes its 1 - erf(z) branch below 1
-    const double y = 0.5 * (z < 1.0 ? 1.0 - cephes::erf_small(z) : cephes::erfc_large(z));
-    return x > 0.0 ? 1.0 - y : y;
-}
-
-__device__ __forceinline__ double norm_pdf(double x) { return exp(-x * x / 2.0) / kSqrt2Pi; }
-
-// (value, index) lexicographic order: smaller value first, lower index on ties.
-__device__ __forceinline__ bool lex_less(double v, long long i, double w, long long j) {
-    return v < w || (v == w && i < j);
-}
-
-__device__ __forceinline__ void wave_lex_min(double& v, long long& i) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        double w = __shfl_xor(v, off);
-        long long j = __shfl_xor(i, off);
-        if (lex_less(w, j, v, i)) { v = w; i = j; }
-    }
 }
 
 // Sum over the 16 lanes of a row group: with the f64 MFMA C/D map (col = lane & 15,
@@ -1973,6 +1892,23 @@ hipError_t mpo::blocked_chol(double* A, int np, double* Dinv, int32_t* info, hip
     return hipGetLastError();
 }
 
+// The two-stage merge of per-wave top-k lists (layout [part][3][k]) into out[acq * k + r]:
+// stage 1 merges G groups of ~64 lists each into `mid` (kTopkMergeGroups x 3 x k entries),
+// stage 2 those into one list, index -1 for missing entries.  gp_ps.hip merges with it too.
+hipError_t mpo::topk_merge(const long long* part_idx, const double* part_val, int nparts, int k, unsigned flags,
+                           long long* mid_idx, double* mid_val, long long* out_idx, double* out_val,
+                           hipStream_t s) {
+    static_assert(kMergeGroups == mpo::kTopkMergeGroups, "the mid lists' size is shared through mpo_internal.h");
+    const int chunk = std::max(64, (nparts + kMergeGroups - 1) / kMergeGroups);
+    const int G = (nparts + chunk - 1) / chunk;
+    hipLaunchKernelGGL(topk_merge_kernel, dim3(G, 3), dim3(256), 0, s, part_idx, part_val, nparts, chunk, k, flags,
+                       mid_idx, mid_val, k, 0);
+    if (hipError_t e = hipGetLastError()) return e;
+    hipLaunchKernelGGL(topk_merge_kernel, dim3(1, 3), dim3(256), 0, s, mid_idx, mid_val, G, G, k, flags, out_idx,
+                       out_val, k, 1);
+    return hipGetLastError();
+}
+
 // ===========================================================================
 extern "C" {
 
@@ -2154,15 +2090,8 @@ static int gp_score_impl(const char* who, const MpoGpModel* model, const double*
     MPO_HIP(launch_scoring(model->dp, model->d, plan, a, ntiles, s, /*fin=*/true, &grid));
     const int nparts = 4 * grid;
     if (k > 0) {
-        // stage 1: G groups of ~64 wave-lists each; stage 2: one list
-        const int chunk = std::max(64, (nparts + kMergeGroups - 1) / kMergeGroups);
-        const int G = (nparts + chunk - 1) / chunk;
-        hipLaunchKernelGGL(topk_merge_kernel, dim3(G, 3), dim3(256), 0, s, w.part_idx, w.part_val, nparts, chunk, k,
-                           flags, w.mid_idx, w.mid_val, k, 0);
-        MPO_LAUNCH_CHECK();
-        hipLaunchKernelGGL(topk_merge_kernel, dim3(1, 3), dim3(256), 0, s, w.mid_idx, w.mid_val, G, G, k, flags,
-                           reinterpret_cast<long long*>(topk_idx), topk_val, k, 1);
-        MPO_LAUNCH_CHECK();
+        MPO_HIP(mpo::topk_merge(w.part_idx, w.part_val, nparts, k, flags, w.mid_idx, w.mid_val,
+                                reinterpret_cast<long long*>(topk_idx), topk_val, s));
     }
     if (ei_argmax) {
         hipLaunchKernelGGL(argmax_from_topk_kernel, dim3(1), dim3(1), 0, s, w.tail_idx,
@@ -2254,18 +2183,10 @@ int mpo_gp_acq_grad_host(const MpoGpModel* model, const double* x_host, int batc
     MPO_GUARD_BEGIN
     MPO_CHECK_ARG(x_host && acq_host && f_host && g_host, "mpo_gp_acq_grad_host: null pointer");
     mpo::StreamDeviceScope on_device(static_cast<hipStream_t>(stream));
-    auto dev_view = [](const void* h) -> void* {
-        hipPointerAttribute_t at{};
-        if (hipPointerGetAttributes(&at, h) != hipSuccess || at.type != hipMemoryTypeHost || !at.devicePointer) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        return at.devicePointer;
-    };
-    void* xd = dev_view(x_host);
-    void* ad = dev_view(acq_host);
-    void* fd = dev_view(f_host);
-    void* gd = dev_view(g_host);
+    void* xd = mpo::pinned_device_view(x_host);
+    void* ad = mpo::pinned_device_view(acq_host);
+    void* fd = mpo::pinned_device_view(f_host);
+    void* gd = mpo::pinned_device_view(g_host);
     MPO_CHECK_ARG(xd && ad && fd && gd, "mpo_gp_acq_grad_host: buffers must be pinned host memory");
     const int rc = mpo_gp_acq_grad(model, static_cast<const double*>(xd), batch, static_cast<const int32_t*>(ad), y_opt,
                                    xi, kappa, static_cast<double*>(fd), static_cast<double*>(gd), stream);

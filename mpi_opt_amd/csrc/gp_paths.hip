@@ -596,18 +596,10 @@ int mpo_gp_paths_grad_host(const MpoGpModel* model, const MpoGpPaths* paths, con
     const char* who = "mpo_gp_paths_grad_host";
     if (const int rc = paths_grad_check(who, model, paths, x_host, draw_host, batch, f_host, g_host)) return rc;
     mpo::StreamDeviceScope on_device(static_cast<hipStream_t>(stream));
-    auto dev_view = [](const void* h) -> void* {
-        hipPointerAttribute_t at{};
-        if (hipPointerGetAttributes(&at, h) != hipSuccess || at.type != hipMemoryTypeHost || !at.devicePointer) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        return at.devicePointer;
-    };
-    void* xd = dev_view(x_host);
-    void* dd = dev_view(draw_host);
-    void* fd = dev_view(f_host);
-    void* gd = dev_view(g_host);
+    void* xd = mpo::pinned_device_view(x_host);
+    void* dd = mpo::pinned_device_view(draw_host);
+    void* fd = mpo::pinned_device_view(f_host);
+    void* gd = mpo::pinned_device_view(g_host);
     MPO_CHECK_ARG(xd && dd && fd && gd, "%s: buffers must be pinned host memory", who);
     for (int b = 0; b < batch; ++b)
         MPO_CHECK_ARG(draw_host[b] >= 0 && draw_host[b] < paths->s, "%s: draw[%d]=%d outside [0, %d)", who, b,

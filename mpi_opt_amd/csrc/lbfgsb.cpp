@@ -1320,6 +1320,29 @@ int mpo_gp_polish_host(const MpoGpModel* model, const double* starts, const int3
     MPO_GUARD_END
 }
 
+int mpo_gp_polish_ps_host(const MpoGpModel* fmodel, const MpoGpModel* tmodel, const double* starts,
+                          const int32_t* acq, int nruns, const double* bounds, const MpoLbfgsbOptions* opts,
+                          double y_opt, double xi, double* x_host, int32_t* acq_host, double* f_host, double* g_host,
+                          double* x_out, double* f_out, int32_t* stats, int32_t* rounds, void* stream) {
+    MPO_GUARD_BEGIN
+    MPO_CHECK_ARG(fmodel && tmodel && acq && x_host && acq_host && f_host && g_host && x_out && f_out,
+                  "mpo_gp_polish_ps_host: null pointer");
+    const int d = fmodel->d;
+    MPO_CHECK_ARG(options_ok(d, nruns, starts, bounds, opts), "mpo_gp_polish_ps_host: bad options / bounds");
+    auto eval = [&](int b, const double* Xp, const int32_t* ids, double* f, double* g) -> int {
+        std::memcpy(x_host, Xp, sizeof(double) * (size_t)b * d);
+        for (int i = 0; i < b; ++i) acq_host[i] = acq[ids[i]];
+        const int rc = mpo_gp_acq_ps_grad_host(fmodel, tmodel, x_host, b, acq_host, y_opt, xi, f_host, g_host, nullptr,
+                                               stream);
+        if (rc != MPO_OK) return rc;
+        std::memcpy(f, f_host, sizeof(double) * b);
+        std::memcpy(g, g_host, sizeof(double) * (size_t)b * d);
+        return 0;
+    };
+    return drive(d, nruns, starts, bounds, to_options(opts), eval, x_out, f_out, stats, rounds);
+    MPO_GUARD_END
+}
+
 int mpo_gp_paths_polish_host(const MpoGpModel* model, const MpoGpPaths* paths, const double* starts,
                              const int32_t* draw, int nruns, const double* bounds, const MpoLbfgsbOptions* opts,
                              double* x_host, int32_t* draw_host, double* f_host, double* g_host, double* x_out,

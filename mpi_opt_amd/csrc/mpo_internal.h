@@ -173,6 +173,17 @@ inline size_t static_lds_bytes(const void* kern) {
     return at.sharedSizeBytes;
 }
 
+// The device view of a pinned (hipHostMalloc / registered) host buffer, which a kernel reads
+// and writes in place; nullptr when `h` is anything else.  The stream's device is current.
+inline void* pinned_device_view(const void* h) {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, h) != hipSuccess || at.type != hipMemoryTypeHost || !at.devicePointer) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return at.devicePointer;
+}
+
 // One pending L-BFGS-B round of one GP refit (gp_fit.hip): `batch` thetas of the
 // problem (X, y, n) in the layout mpo_gp_lml_grad_host uses.  lml_launch_rounds
 // evaluates the rounds of several refits in one launch set (same d, every n
@@ -194,6 +205,14 @@ int lml_launch_rounds(const LmlRound* r, int count, hipStream_t s);
 // triangle and the full 32 x 32 diagonal blocks.  Dinv: np * 32 doubles of scratch.
 // *info (device) = 0, or the first failed column + 1.  All sums in a fixed order.
 hipError_t blocked_chol(double* A, int np, double* Dinv, int32_t* info, hipStream_t s);
+
+// The scoring kernels' two-stage top-k merge (gp.hip: topk_merge_kernel) over nparts lists
+// in the layout [part][3][k] (acquisition slots EI, PI, LCB; only those in `flags` are
+// read), ties to the lowest index: out_idx / out_val [acq * k + r], index -1 where fewer
+// than k entries exist.  mid_idx / mid_val: kTopkMergeGroups * 3 * k entries of scratch.
+constexpr int kTopkMergeGroups = 256;
+hipError_t topk_merge(const long long* part_idx, const double* part_val, int nparts, int k, unsigned flags,
+                      long long* mid_idx, double* mid_val, long long* out_idx, double* out_val, hipStream_t s);
 
 }  // namespace mpo
 

@@ -387,6 +387,107 @@ class DeviceGP:
         return (mu, sd) if return_std else mu
 
 
+# -- cost-aware acquisitions (EIps / PIps): two models over the same observations ----------
+def _check_pair(fgp, tgp):
+    if fgp.device != tgp.device or (fgp.n, fgp.d) != (tgp.n, tgp.d):
+        raise ValueError(f"the objective and the log-time model must share device and shape: "
+                         f"n {fgp.n} / {tgp.n}, d {fgp.d} / {tgp.d}, {fgp.device} / {tgp.device}")
+
+
+def score_ps(fgp, tgp, cand, y_opt, acqs=("EI",), xi=0.01, k=0, want_values=True, want_inv_t=True):
+    """``mpo_gp_acq_ps_score``: the cost-aware acquisitions of skopt's "EIps" / "PIps" over
+    the candidates, ``v = a * inv_t`` with ``a`` = -EI / -PI under ``fgp`` (the objective's
+    :class:`DeviceGP`) and ``inv_t = exp(-mu + sd^2 / 2)`` under ``tgp`` (the one on log
+    time).  ``acqs`` names plain "EI" / "PI".  Returns device tensors: ``values`` {acq: (m,)},
+    ``inv_t`` (m,), ``topk`` {acq: (idx int64 (k,), val (k,))}."""
+    _check_pair(fgp, tgp)
+    c = fgp.as_candidates(cand)
+    m = c.shape[0]
+    flags = 0
+    for a in acqs:
+        if a not in ("EI", "PI"):
+            raise ValueError(f"score_ps: acquisition {a!r}: 'EI' or 'PI'")
+        flags |= _lib.ACQ_FLAGS[a]
+    L = lib()
+    need = L.mpo_gp_acq_ps_ws_bytes(ctypes.byref(fgp.model), ctypes.byref(tgp.model), m, int(k))
+    if need == 0:
+        raise _lib.MpoError("mpo_gp_acq_ps_ws_bytes rejected the shape")
+    if getattr(fgp, "_ps_ws", None) is None or fgp._ps_ws.numel() < need:
+        fgp._ps_ws = torch.empty(need, dtype=torch.uint8, device=fgp.device)
+    dev = fgp.device
+    vals = torch.empty(2, m, dtype=torch.float64, device=dev) if want_values else None
+    inv_t = torch.empty(m, dtype=torch.float64, device=dev) if want_inv_t else None
+    tki = torch.empty(2, max(k, 1), dtype=torch.int64, device=dev)
+    tkv = torch.empty(2, max(k, 1), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(L.mpo_gp_acq_ps_score(ctypes.byref(fgp.model), ctypes.byref(tgp.model), ptr(c), m, float(y_opt),
+                                    float(xi), flags, ptr(vals), ptr(inv_t), int(k), ptr(tki) if k else None,
+                                    ptr(tkv) if k else None, ptr(fgp._ps_ws), fgp._ps_ws.numel(),
+                                    _lib.stream_handle(dev)), "mpo_gp_acq_ps_score")
+    out = {"values": {}, "inv_t": inv_t, "topk": {}}
+    for a in acqs:
+        r = _lib.ACQ_ROW[a]
+        if vals is not None:
+            out["values"][a] = vals[r]
+        if k:
+            out["topk"][a] = (tki[r, :k], tkv[r, :k])
+    return out
+
+
+def acq_grad_ps(fgp, tgp, X, acq_codes, y_opt, xi=0.01, want_parts=False):
+    """``mpo_gp_acq_ps_grad_host``: value and gradient of the cost-aware acquisition
+    ``acq_codes[b]`` (MPO_ACQ_EI / MPO_ACQ_PI) at the rows of X (B, d), through ``fgp``'s
+    pinned round buffers.  Returns numpy ``(f (B,), g (B, d))``, with ``want_parts`` also
+    ``parts (B, 4) = (a, inv_t, mu_t, s_t)``."""
+    _check_pair(fgp, tgp)
+    X = np.asarray(X, dtype=np.float64).reshape(-1, fgp.d)
+    B, d = X.shape
+    fgp._ensure_ag(B)
+    xn, an, fn, gn = fgp._ag_np
+    xn[:B * d] = X.reshape(-1)
+    an[:B] = acq_codes
+    xp, ap, fp, gp = fgp._ag_ptrs
+    parts = None
+    if want_parts:
+        if getattr(fgp, "_ag_parts", None) is None or fgp._ag_parts.numel() < 4 * B:
+            fgp._ag_parts = torch.empty(4 * max(16, B), dtype=torch.float64).pin_memory()
+        parts = fgp._ag_parts
+    rc = lib().mpo_gp_acq_ps_grad_host(ctypes.byref(fgp.model), ctypes.byref(tgp.model), xp, B, ap, float(y_opt),
+                                       float(xi), fp, gp, ptr(parts), fgp._ag_stream)
+    if rc != 0:
+        check(rc, "mpo_gp_acq_ps_grad_host")
+    f, g = fn[:B].copy(), gn[:B * d].reshape(B, d).copy()
+    if want_parts:
+        return f, g, parts.numpy()[:4 * B].reshape(B, 4).copy()
+    return f, g
+
+
+def polish_ps(fgp, tgp, starts, acq_codes, y_opt, xi, bounds, ftol, maxiter=20, gtol=1e-5, maxfun=15000):
+    """``mpo_gp_polish_ps_host``: :meth:`DeviceGP.polish` on the cost-aware objective.
+    Returns [(x, f)] per run."""
+    _check_pair(fgp, tgp)
+    starts = np.ascontiguousarray(np.asarray(starts, dtype=np.float64))
+    B, d = starts.shape
+    if d != fgp.d:
+        raise ValueError(f"polish starts must be (B, {fgp.d}), got {starts.shape}")
+    fgp._ensure_ag(B)
+    codes = np.ascontiguousarray(np.asarray(acq_codes, dtype=np.int32))
+    b = np.ascontiguousarray(np.asarray(bounds, dtype=np.float64).reshape(d, 2))
+    opts = _lib.MpoLbfgsbOptions(ftol, gtol, maxiter, maxfun, 10, 20)
+    x = np.empty((B, d))
+    f = np.empty(B)
+    stats = np.empty((B, 4), np.int32)
+    rounds = ctypes.c_int32(0)
+    xp, ap, fp, gp = fgp._ag_ptrs
+    rc = lib().mpo_gp_polish_ps_host(ctypes.byref(fgp.model), ctypes.byref(tgp.model), starts.ctypes.data,
+                                     codes.ctypes.data, B, b.ctypes.data, ctypes.byref(opts), float(y_opt), float(xi),
+                                     xp, ap, fp, gp, x.ctypes.data, f.ctypes.data, stats.ctypes.data,
+                                     ctypes.byref(rounds), fgp._ag_stream)
+    if rc != 0:
+        check(rc, "mpo_gp_polish_ps_host")
+    return [(x[r], float(f[r])) for r in range(B)]
+
+
 def _normalise(y):
     """normalize_y=True (sklearn _gpr.py:273-277): (y_mean, y_std, y_norm)."""
     y_mean = float(np.mean(y))

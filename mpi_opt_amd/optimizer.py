@@ -156,6 +156,49 @@ class GPModel:
         return paths
 
 
+class PsModel:
+    """The surrogate of a cost-aware acquisition ("EIps" / "PIps"): skopt's
+    ``MultiOutputRegressor(clone(base_estimator))`` over the told ``(value, log time)``
+    pairs.  ``estimators_ == [f_model, tau_model]``, two :class:`GPModel` on the same
+    transformed points: the objective's and the one on log time."""
+
+    def __init__(self, f_model, tau_model):
+        self.estimators_ = [f_model, tau_model]
+
+    @property
+    def y(self):
+        """The objective values (the log-times are ``estimators_[1].y``)."""
+        return self.estimators_[0].y
+
+    # the optimizer releases and re-homes a model's device state through these two names
+    @property
+    def _dev(self):
+        return self.estimators_[0]._dev
+
+    @_dev.setter
+    def _dev(self, v):
+        for e in self.estimators_:
+            e._dev = v
+
+    @property
+    def device(self):
+        return self.estimators_[0].device
+
+    @device.setter
+    def device(self, v):
+        for e in self.estimators_:
+            e.device = v
+
+
+#: the cost-aware acquisitions: the told results are (value, time) pairs
+PS_ACQS = ("EIps", "PIps")
+
+
+def acq_code(acq):
+    """The MPO_ACQ_* flag of an acquisition name; "EIps" / "PIps" carry their plain one's."""
+    return _lib.ACQ_FLAGS[acq[:-2] if acq in PS_ACQS else acq]
+
+
 #: relative jitters (times amp) tried in turn on the sample covariance's diagonal
 JITTER_LADDER = (1e-8, 1e-6, 1e-4)
 
@@ -181,16 +224,27 @@ def polish_lockstep(model, starts, acqs, y_opt, xi, kappa, bounds, maxiter=20, d
     that each round of evaluations is one ``mpo_gp_acq_grad`` launch over all live
     runs.  ``driver="native"``: the whole polish in ``mpo_gp_polish_host`` (the host
     L-BFGS-B of libmpo.so, no GIL held); "scipy": scipy's setulb driven from
-    Python.  Returns [(x, f)] per run."""
+    Python.  A :class:`PsModel` with "EIps" / "PIps" runs takes the cost-aware objective
+    (``mpo_gp_polish_ps_host`` / ``mpo_gp_acq_ps_grad_host``; ``kappa`` unused).
+    Returns [(x, f)] per run."""
     from .gp_fit import FMIN_FTOL, _Lockstep, _setulb, lbfgsb_batched
 
-    codes = np.array([_lib.ACQ_FLAGS[a] for a in acqs], dtype=np.int32)
+    codes = np.array([acq_code(a) for a in acqs], dtype=np.int32)
+    ps = isinstance(model, PsModel)
+    if ps:
+        from .gp import acq_grad_ps, polish_ps
+
+        fdev, tdev = (e.dev for e in model.estimators_)
     if driver == "native":
+        if ps:
+            return polish_ps(fdev, tdev, np.array(starts), codes, y_opt, xi, bounds, ftol=FMIN_FTOL, maxiter=maxiter)
         return model.dev.polish(np.array(starts), codes, y_opt, xi, kappa, bounds, ftol=FMIN_FTOL, maxiter=maxiter)
     if driver != "scipy":
         raise ValueError(f"driver {driver!r}: 'native' or 'scipy'")
 
     def evaluate(X, ids):
+        if ps:
+            return acq_grad_ps(fdev, tdev, X, codes[ids], y_opt, xi)
         return model.dev.acq_grad(X, codes[ids], y_opt, xi, kappa)
 
     if _setulb() is not None:        # one thread drives every run (setulb reverse communication)
@@ -274,6 +328,47 @@ def _gather_winners(X, index_lists):
     return dict(zip(idx.tolist(), rows))
 
 
+def _device_topk_ps(est, X, y_opt, acqs, xi, k):
+    """``blocks._device_topk`` for a :class:`PsModel`: {acq: (values (k,), indices (k,))} of
+    the cost-aware acquisitions ``acqs`` ("EIps" / "PIps") by ``mpo_gp_acq_ps_score``; past
+    MPO_TOPK_MAX a stable sort of the whole value rows."""
+    import torch
+
+    from .gp import score_ps
+
+    fdev, tdev = (e.dev for e in est.estimators_)
+    plain = tuple(a[:-2] for a in acqs)
+    if k <= _lib.MPO_TOPK_MAX:
+        sc = score_ps(fdev, tdev, X, y_opt, acqs=plain, xi=xi, k=k, want_values=False, want_inv_t=False)
+        return {a: (sc["topk"][p][1].cpu().numpy(), sc["topk"][p][0].cpu().numpy()) for a, p in zip(acqs, plain)}
+    sc = score_ps(fdev, tdev, X, y_opt, acqs=plain, xi=xi, k=0, want_values=True, want_inv_t=False)
+    out = {}
+    for a, p in zip(acqs, plain):
+        v, i = torch.sort(sc["values"][p], stable=True)
+        out[a] = (v[:k].cpu().numpy(), i[:k].cpu().numpy())
+    return out
+
+
+def _split_pairs(y, n):
+    """The told results of a cost-aware acquisition as ``(values, log-times)``: one
+    ``(value, time)`` pair (``n`` is None) or a sequence of ``n`` pairs.  ``ValueError`` for
+    anything else -- a scalar, another length, a time that is not finite and positive."""
+    def pair(p):
+        if np.ndim(p) != 1 or len(p) != 2:
+            raise ValueError(f"tell: a cost-aware acquisition takes (value, time) pairs, got {p!r}")
+        v, t = float(p[0]), float(p[1])
+        if not (np.isfinite(t) and t > 0):
+            raise ValueError(f"tell: the time of a (value, time) pair must be finite and > 0, got {t!r}")
+        return v, float(np.log(t))
+
+    if n is None:
+        return pair(y)
+    if np.ndim(y) == 0 or len(y) != n:
+        raise ValueError(f"tell: {n} points need {n} (value, time) pairs")
+    pairs = [pair(p) for p in y]
+    return [p[0] for p in pairs], [p[1] for p in pairs]
+
+
 #: ask(n, strategy): skopt's three constant liars, then "thompson" (an addition of this
 #: build, last so that the encoded index of the others does not move)
 STRATEGIES = ("cl_min", "cl_mean", "cl_max", "thompson")
@@ -308,13 +403,14 @@ class ChainJob:
     job can run later, on another thread, stream, process or GPU, and give the
     same points.  Picklable (no device state)."""
 
-    __slots__ = ("config", "Xi", "yi", "gains", "initial_samples", "n_initial_points", "seed", "n_points",
+    __slots__ = ("config", "Xi", "yi", "ti", "gains", "initial_samples", "n_initial_points", "seed", "n_points",
                  "strategy", "trace", "cost")
 
     def __init__(self, opt, seed, n_points, strategy):
         self.config = opt._config()
         self.Xi = [list(x) for x in opt.Xi]
         self.yi = list(opt.yi)
+        self.ti = list(opt.ti)          # log-times of a cost-aware acquisition's pairs, else empty
         self.gains = np.copy(opt.gains_) if hasattr(opt, "gains_") else None
         self.initial_samples = opt._initial_samples
         self.n_initial_points = opt.n_initial_points_
@@ -337,7 +433,9 @@ class ChainJob:
 
     def encode(self):
         """(meta int64 [META], blob f64): the job without its config (sent once per
-        search).  Points cross as (value, type code) pairs (collectives.encode_points)."""
+        search).  Points cross as (value, type code) pairs (collectives.encode_points).
+        A ``ti`` column follows ``yi`` exactly when the config's ``acq_func`` is a
+        cost-aware one (the receiver decodes with the same config)."""
         from .collectives import encode_points
 
         if not isinstance(self.seed, (int, np.integer)):
@@ -348,6 +446,10 @@ class ChainJob:
         xv, xc = encode_points(self.Xi) if n else (np.zeros((0, 0)), np.zeros((0, 0)))
         d = xv.shape[1] if n else 0
         parts = [xv.ravel(), xc.ravel(), np.asarray(self.yi, dtype=np.float64)]
+        if self.config["acq_func"] in PS_ACQS:
+            if len(self.ti) != n:
+                raise ValueError(f"ChainJob.encode: {len(self.ti)} log-times for {n} values")
+            parts.append(np.asarray(self.ti, dtype=np.float64))
         if self.gains is not None:
             parts.append(np.asarray(self.gains, dtype=np.float64).ravel())
         n_init = -1
@@ -374,6 +476,9 @@ class ChainJob:
         xc = blob[o:o + n * d].reshape(n, d); o += n * d
         job.Xi = decode_points(xv, xc)
         job.yi = [float(v) for v in blob[o:o + n]]; o += n
+        job.ti = []
+        if config["acq_func"] in PS_ACQS:
+            job.ti = [float(v) for v in blob[o:o + n]]; o += n
         job.gains = None
         if ng >= 0:
             job.gains = np.array(blob[o:o + ng], dtype=np.float64); o += ng
@@ -397,7 +502,7 @@ class ChainJob:
             opt.gains_ = np.copy(self.gains)
         opt.trace = [] if self.trace else None
         if self.Xi:
-            opt._tell([list(x) for x in self.Xi], list(self.yi))
+            opt._tell([list(x) for x in self.Xi], list(self.yi), logt=list(self.ti) if opt._ps else None)
         return opt
 
     def run(self, device=None, scorer=None):
@@ -406,6 +511,15 @@ class ChainJob:
         if self.strategy == "thompson":
             return _thompson_batch(opt, self.n_points), opt.trace
         return _lie_loop(opt, self.n_points, self.strategy), opt.trace
+
+
+def lie_time(ti, strategy):
+    """The time half of a constant-liar lie under a cost-aware acquisition: the min / mean /
+    max of the told log-times for cl_min / cl_mean / cl_max (0.0 with none told).  It is a
+    log-time already and is told as one."""
+    if not ti:
+        return 0.0
+    return float({"cl_min": np.min, "cl_mean": np.mean, "cl_max": np.max}[strategy](ti))
 
 
 def _lie_loop(opt, n_points, strategy):
@@ -423,7 +537,7 @@ def _lie_loop(opt, n_points, strategy):
             lie = np.mean(opt.yi) if opt.yi else 0.0
         else:
             lie = np.max(opt.yi) if opt.yi else 0.0
-        opt._tell(x, lie, append=append)
+        opt._tell(x, lie, append=append, logt=lie_time(opt.ti, strategy) if opt._ps else None)
         # only the newest surrogate is used again (gains, the next proposal):
         # release the older ones' device factorisations as the chain grows
         for m in opt.models[:-1]:
@@ -655,6 +769,18 @@ class Optimizer:
     device top-k width (``MPO_TOPK_MAX`` = 8); the acquisition rows are then
     sorted whole on the device instead.
 
+    ``acq_func`` "EIps" / "PIps" (skopt's cost-aware acquisitions): ``tell`` then takes
+    ``(value, time)`` pairs -- ``tell(x, (y, t))`` or ``tell(X, [(y, t), ...])``, every ``t``
+    finite and > 0, anything else a ``ValueError`` before any state changes.  ``yi`` stays the
+    flat list of values and ``ti`` holds the log-times.  Every fit runs twice with the same
+    seed, on the values and on the log-times; ``models[-1]`` is a :class:`PsModel`
+    (``estimators_ == [f_model, tau_model]``), and the value that is minimised is
+    ``-EI(x) * exp(-mu_t + sd_t^2 / 2)`` (or -PI), scored by ``mpo_gp_acq_ps_score`` and
+    polished on ``mpo_gp_acq_ps_grad``.  ``y_opt`` is the minimum of the VALUES (the
+    documented meaning).  A constant-liar lie is the pair of the same statistic of ``yi``
+    and of ``ti``.  No gp_hedge; a ``scorer`` is ignored (the asking rank scores locally);
+    refused together with ``lie_refit="never"`` or the "thompson" strategy.
+
     ``lie_refit`` ("every" | "never", an addition of this build): "every" is skopt's
     ``ask(n)``, a hyper-parameter refit per constant-liar lie.  "never" departs from it:
     the lies of a batch keep the theta of the copy's newest model and extend its
@@ -729,8 +855,14 @@ class Optimizer:
         # receives the cooked estimator (no draw), and every refit clones it, so the
         # GP restarts draw from the same seed at every fit.
         self._gp_seed = self.rng.randint(0, np.iinfo(np.int32).max) if _gp_seed is None else _gp_seed
-        if acq_func not in ("gp_hedge", "EI", "PI", "LCB"):
+        if acq_func not in ("gp_hedge", "EI", "PI", "LCB") + PS_ACQS:
             raise ValueError(f"acq_func {acq_func!r} not supported")
+        if acq_func in PS_ACQS and lie_refit == "never":
+            raise ValueError(f'acq_func {acq_func!r} with lie_refit="never" is not supported: the fixed-theta '
+                             "append serves one model, a cost-aware acquisition holds two")
+        if acq_func in PS_ACQS and batch_strategy == "thompson":
+            raise ValueError(f'acq_func {acq_func!r} with the "thompson" strategy is not supported: a Thompson '
+                             "batch draws from the objective's posterior alone")
         self.acq_func = acq_func
         self.acq_func_kwargs = dict(acq_func_kwargs or {})
         self.eta = self.acq_func_kwargs.get("eta", 1.0)
@@ -753,6 +885,9 @@ class Optimizer:
         if acq_func == "gp_hedge":
             self.gains_ = np.zeros(3)
         self.Xi, self.yi, self.models = [], [], []
+        # "EIps" / "PIps": the log of the time of every told (value, time) pair, next to yi
+        # (which stays the flat list of values); empty under every other acquisition
+        self.ti = []
         self.cache_ = {}
         self.trace = None       # a list here records each refit (theta, top-k, polish, pick) for parity tests
         # optional: runs ask(n) batches asynchronously (mpi_opt_amd.chains); ask then
@@ -766,7 +901,13 @@ class Optimizer:
         d.setdefault("lie_refit", "every")
         d.setdefault("candidates", "host")
         d.setdefault("batch_strategy", "cl_min")
+        d.setdefault("ti", [])
         self.__dict__.update(d)
+
+    @property
+    def _ps(self):
+        """True under a cost-aware acquisition: results are (value, time) pairs."""
+        return self.acq_func in PS_ACQS
 
     def _config(self):
         """The constructor arguments a copy() shares with this optimizer."""
@@ -787,6 +928,8 @@ class Optimizer:
             strategy = self.batch_strategy
         if strategy not in STRATEGIES:
             raise ValueError(f"strategy {strategy!r}")
+        if strategy == "thompson" and self._ps:
+            raise ValueError(f'acq_func {self.acq_func!r} with the "thompson" strategy is not supported')
         if strategy == "thompson" and self.base_estimator_ == "gp":
             # refused here, before the copy's fit (_thompson_step checks again)
             thompson_config(self.acq_optimizer_kwargs, self.n_points, n_points - max(self._n_initial_points, 0))
@@ -822,14 +965,22 @@ class Optimizer:
             x = resolve(x)
         elif len(x) and isinstance(x[0], LazyPoint):
             x = [resolve(v) for v in x]
-        if len(x) and isinstance(x[0], (list, tuple, np.ndarray)):
+        batch = len(x) and isinstance(x[0], (list, tuple, np.ndarray))
+        if self._ps:
+            y, logt = _split_pairs(y, len(x) if batch else None)     # raises before any state changes
+            return self._tell(x, y, fit=fit, logt=logt)
+        if batch:
             if not np.ndim(y) == 1 or len(y) != len(x):
                 raise ValueError("tell: X and y must have matching lengths")
         return self._tell(x, y, fit=fit)
 
-    def _tell(self, x, y, fit=True, append=False):
+    def _tell(self, x, y, fit=True, append=False, logt=None):
+        """``logt``: under a cost-aware acquisition the LOG of the time(s) that go with ``y``
+        (``tell`` takes the logarithm; a constant-liar lie is a log-time already)."""
         batch = len(x) and isinstance(x[0], (list, tuple, np.ndarray))
         n_new = len(y) if batch else 1
+        if self._ps and (logt is None or (len(logt) if batch else 1) != n_new):
+            raise ValueError(f"acq_func {self.acq_func!r}: every told value needs its time")
         if fit and self._n_initial_points - n_new <= 0 and self.base_estimator_ == "gp":
             _check_gp_size(len(self.yi) + n_new)        # before the points are taken: nothing changes on error
         if batch:
@@ -840,6 +991,8 @@ class Optimizer:
             self.Xi.append(list(x))
             self.yi.append(float(y))
             self._n_initial_points -= 1
+        if self._ps:
+            self.ti.extend([float(v) for v in logt] if batch else [float(logt)])
         self.cache_ = {}
         if fit and self._n_initial_points <= 0 and self.base_estimator_ == "gp":
             # a lie of a lie_refit="never" batch keeps the theta of the newest model when that
@@ -855,9 +1008,18 @@ class Optimizer:
         y = np.asarray(self.yi, dtype=float)
         t0 = time.perf_counter()
         amp, ls, noise = fit_gp_hyperparameters(Xt, y, random_state=self._gp_seed, device=self.device)
+        if self._ps:
+            # skopt's MultiOutputRegressor(clone(base_estimator)): the same estimator, so the
+            # same seed and the same restart starts, fitted to the log-times
+            lt = np.asarray(self.ti, dtype=float)
+            theta_t = fit_gp_hyperparameters(Xt, lt, random_state=self._gp_seed, device=self.device)
         t1 = time.perf_counter()
         est = GPModel(Xt, y, amp, ls, noise, device=self.device)
         est.dev                                   # the device posterior (mpo_gp_prepare)
+        if self._ps:
+            tau = GPModel(Xt, lt, *theta_t, device=self.device)
+            tau.dev
+            est = PsModel(est, tau)
         self._propose(est, t0, t1, time.perf_counter())
 
     def _append_and_propose(self):
@@ -898,8 +1060,12 @@ class Optimizer:
         top = self._score_topk(est, X, y_opt, xi, kappa, k)
         t4 = time.perf_counter()
         t_polish = 0.0
-        rec = {"theta": (est.amp, est.length_scale.copy(), est.noise), "top": dict(top), "polished": {}} \
+        fm = est.estimators_[0] if self._ps else est
+        rec = {"theta": (fm.amp, fm.length_scale.copy(), fm.noise), "top": dict(top), "polished": {}} \
             if self.trace is not None else None
+        if rec is not None and self._ps:
+            tau = est.estimators_[1]
+            rec["theta_t"] = (tau.amp, tau.length_scale.copy(), tau.noise)
         if cand_seed is not None:
             # X stays the device tensor; the host sees the winning rows only
             won = _gather_winners(X, [top[a] for a in self.cand_acq_funcs_])
@@ -946,8 +1112,12 @@ class Optimizer:
         """skopt's ``np.argsort(values)[:k]`` per acquisition (lowest index first on
         ties).  The device top-k holds up to MPO_TOPK_MAX entries; a larger
         ``n_restarts_optimizer`` takes the full value rows and a stable sort.  With
-        a ``scorer`` (e.g. blocks.ShardedScorer) the candidates are split over GPUs."""
+        a ``scorer`` (e.g. blocks.ShardedScorer) the candidates are split over GPUs.
+        A cost-aware acquisition ("EIps" / "PIps") IGNORES the scorer: the asking rank
+        scores all candidates locally against both models (``mpo_gp_acq_ps_score``)."""
         acqs = tuple(self.cand_acq_funcs_)
+        if self._ps:
+            return {a: idx for a, (vals, idx) in _device_topk_ps(est, X, y_opt, acqs, xi, k).items()}
         if self.scorer is not None:
             return self.scorer(est, X, y_opt, acqs, xi, kappa, k)
         from .blocks import _device_topk

@@ -71,6 +71,10 @@ class AskTellScheduler:
     ``comm`` needs ``Get_size``, ``send(obj, dest, tag)``, ``irecv(source, tag)``
     (returning an object with ``test() -> (done, value)``) and ``Barrier`` --
     an mpi4py communicator or :class:`~mpi_opt_amd.blocks.PopulationComm`.
+
+    ``cost_fn`` (callable(params) -> a positive cost, default None): for an optimizer with a
+    cost-aware acquisition ("EIps" / "PIps"), every result is told as the pair
+    ``(fom, cost_fn(params))``.  The reference's own ``Coordinator`` knows no such thing.
     """
 
     #: callable(dimensions, random_state) -> optimizer (tests inject stubs)
@@ -78,13 +82,14 @@ class AskTellScheduler:
     random_state = 13579            # coordinator.py:33
 
     def __init__(self, comm, num_blocks, dimensions, checkpoint="coordinator.pkl", target_fom=None,
-                 verbose=False, optimizer_kwargs=None):
+                 verbose=False, optimizer_kwargs=None, cost_fn=None):
         self.comm = comm
         self.num_blocks = int(num_blocks)
         self.dimensions = dimensions
         self.checkpoint = checkpoint
         self.target_fom = target_fom
         self.verbose = verbose
+        self.cost_fn = cost_fn
         self.optimizer = type(self).optimizer_factory(dimensions, self.random_state, **(optimizer_kwargs or {}))
         self.state = SearchState()
         self.inflight = {}          # block -> _Launch
@@ -130,6 +135,8 @@ class AskTellScheduler:
             return
         xs = [p for p, _ in st.unsent]
         ys = [f for _, f in st.unsent]
+        if self.cost_fn is not None:
+            ys = [(f, self.cost_fn(p)) for p, f in st.unsent]
         t0 = time.perf_counter()
         res = self.optimizer.tell(xs, ys)
         self.timings["tell_s"] += time.perf_counter() - t0

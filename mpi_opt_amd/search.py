@@ -125,7 +125,27 @@ def make_parser():
                         "from its picked candidate by L-BFGS-B (20 iterations) instead of stopping at the "
                         "candidate (NOT the reference's semantics; nothing is known about its effect on "
                         "search quality)")
+    p.add_argument("--acq-func", default="gp_hedge", choices=list(ACQ_FUNCS), dest="acq_func",
+                   help="the optimizer's acquisition function (skopt's names; the reference's Coordinator uses the "
+                        "default, gp_hedge).  EIps / PIps are skopt's cost-aware acquisitions: every result is told "
+                        "with a cost, and the acquisition is divided by the expected cost.  The cost here is the "
+                        "MODELLED training GFLOP per sample of the trial's architecture, not a measured time, and "
+                        "it ignores early stopping")
     return p
+
+
+#: --acq-func: skopt's acquisition functions
+ACQ_FUNCS = ("gp_hedge", "EI", "PI", "LCB", "EIps", "PIps")
+
+
+def modelled_cost_fn(provider):
+    """cost_fn of a cost-aware search: params -> the modelled training GFLOP per sample of the
+    trial (``models.flops_of_params``).  A model of the architecture, not a measurement; early
+    stopping does not enter it."""
+    from .models import flops_of_params
+
+    names = [p.name for p in provider.parameters]
+    return lambda params: flops_of_params(provider.model_fn, names, params) * 1e-9
 
 
 def check_sanity(args):
@@ -259,12 +279,18 @@ def run_search(args, x=None, y=None, log=print, progress=None, on_population=Non
         opt_kw["acq_optimizer_kwargs"]["ts_sampler"] = args.thompson_sampler
     if getattr(args, "thompson_polish", False):
         opt_kw["acq_optimizer_kwargs"]["ts_polish"] = True    # each draw minimised from its pick
+    cost_fn = None
+    if args.acq_func != "gp_hedge":
+        opt_kw["acq_func"] = args.acq_func
+    if args.acq_func.endswith("ps"):
+        cost_fn = modelled_cost_fn(provider)              # told as (fom, cost) pairs
     if chains is not None:
         opt_kw["chain_executor"] = chains                 # ask batches run concurrently (mpi_opt_amd.chains)
     if dist is not None:
         opt_kw["scorer"] = ShardedScorer(evaluator)       # candidates split M/W over the GPUs
     sched = AskTellScheduler(comm, num_blocks, provider.parameters, checkpoint=args.checkpoint,
-                             target_fom=args.target_objective, verbose=args.verbose, optimizer_kwargs=opt_kw)
+                             target_fom=args.target_objective, verbose=args.verbose, optimizer_kwargs=opt_kw,
+                             cost_fn=cost_fn)
     from . import optimizer as _opt_mod
 
     _opt_mod.reset_stats()
