@@ -26,9 +26,12 @@ right-hand sides, the most whose solutions fit the LDS.
 
 Polish points never lie exactly on an observation: there the sign of the rounded
 ``amp - |v|^2`` decides between ``sd = 0`` (EI / PI answer 0, ``sd_g = 0``) and a tiny
-positive sd, and no reference can say which way fp64 falls.  The kernel's ``sd <= 0``
-branches stay covered by reading only; every point here has exact ``var_n >= 1e-6 amp``
-(the host test fails if one does not -- no point is ever dropped).
+positive sd, and no reference can say which way fp64 falls -- under a positive noise term.
+Every point here has exact ``var_n >= 1e-6 amp`` (the host test fails if one does not -- no
+point is ever dropped).  The kernel's ``sd <= 0`` branches run in
+``tests/test_acq_sd_zero_gpu.py``, on models with a negative noise term
+(``ps_cases.sd0_inputs``): there the variance at an observation is ``-amp`` or lower in every
+precision and the inputs decide the branch.
 """
 import functools
 import math
@@ -400,7 +403,8 @@ def polish_inputs(name):
     of an observation with itself would lie on it).  ``y_opt`` is the median target, not the
     best one: z = (y_opt - xi - mu) / sd then takes both signs and stays inside +-38 at nearly
     every point, where with the minimum EI and PI underflow to 0 at most points of the dense
-    models (z down to -128 at n = 915) and their bars would hold vacuously."""
+    models (z down to -128 at n = 915) and their bars would hold vacuously.  The minimum runs
+    in ``tests/test_acq_ps_edges_gpu.py``, which asserts exact zeros at the underflowed points."""
     from oracle import gp_ei as O
 
     c = polish_by_name(name)
