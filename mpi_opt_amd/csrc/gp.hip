@@ -22,14 +22,15 @@
 //                        fit the LDS (n <= 2048): K* one panel of observations at a
 //                        time, later panels' partial rows in the score workspace
 //   topk_merge_kernel    workgroup top-k lists -> global top-k (lowest index ties)
+//   acq_grad_kernel      acquisition value + gradient at a few points (the polish objective),
+//                        a caller of gp_grad.h's posterior_grad / acq_value_grad
 //
 // Why the triangular form: skopt evaluates sd^2 = amp - k^T K_inv k with an
 // explicit K_inv (86 kFLOP/candidate at N=200, catastrophic cancellation);
 // sd^2 = amp - ||L^-1 k||^2 is the same posterior with half the MFMA work and
 // ~1000x less rounding error (DESIGN.md "GP posterior formulation").
 
-#include "mpo_internal.h"
-#include "gp_acq_math.h"
+#include "gp_grad.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1028,7 +1029,7 @@ inline int pad_dims(int d) {
     return -1;
 }
 
-constexpr size_t kMaxLds = 160 * 1024;
+using mpo::kMaxLds;
 constexpr int kMergeGroups = 256;  // stage-1 top-k merge groups
 // Scoring grid bound: the resident capacity is <= 8 workgroups of 4 waves per CU
 // (32 waves), 256 CUs on MI355X; workspace for top-k lists is sized from this.
@@ -1560,158 +1561,26 @@ hipError_t append_factor(const double* xs, int n, int dp, double amp, double dia
 }
 
 // ---------------------------------------------------------------------------
-// Acquisition value + gradient at a few points: the objective of skopt's
-// L-BFGS-B polish of the best n_restarts_optimizer candidates per acquisition
-// (skopt optimizer.py _tell -> fmin_l_bfgs_b(gaussian_acquisition_1D, ...,
-// maxiter=20); gaussian_acquisition_1D / gaussian_ei/pi/lcb(return_grad=True) and
-// GaussianProcessRegressor.predict(return_mean_grad, return_std_grad)).  All
-// polishes of one ask step run in lockstep, so one launch carries one point per
-// live L-BFGS-B run: one workgroup per point, the posterior as in the scoring
-// kernel but with the explicit derivative of k* (skopt gpr.py):
-//   dk_i/dx_j  = c_i (x_j - X_ij) / ls_j^2,  c_i = -(5/3) amp (1 + t_i) e^-t_i
-//   dmu/dx     = y_std dk^T alpha
-//   dsd/dx     = -y_std dk^T (W^T W k*) / sd_n,  W = L^-1
-// LDS: k*, c (n each), v = W k* (n), one per-wave partial of W^T v per wave (NW n).
-// NW = 16 waves per point while (3 + NW) n doubles fit the LDS (n <= ~1000; the
-// 4-wave form past it): the two triangular mat-vecs are the kernel's serial work,
-// 16 waves cut them 4x (n = 512: 214 -> see DESIGN §3.1b round trip per launch).
+// Acquisition value + gradient at a few points, the polish objective: one workgroup of NW
+// waves per point b, f[b] and g[b][d] of acquisition acq[b] from mpo::posterior_grad and
+// mpo::acq_value_grad (gp_grad.h, shared with gp_ps.hip's cost-aware kernel).
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void acq_grad_kernel(
-        int n, int d, int dp, double amp, double y_mean, double y_std, const double* __restrict__ xs,
-        const double* __restrict__ ls, const double* __restrict__ alpha, const double* __restrict__ W,
-        const double* __restrict__ x, const int32_t* __restrict__ acq, double y_opt, double xi, double kappa,
-        double* __restrict__ f, double* __restrict__ g) {
+        int n, int d, mpo::GradModel gm, const double* __restrict__ x, const int32_t* __restrict__ acq, double y_opt,
+        double xi, double kappa, double* __restrict__ f, double* __restrict__ g) {
     extern __shared__ double sm[];
-    double* kk = sm;              // [n]
-    double* cc = kk + n;          // [n]
-    double* vv = cc + n;          // [n]
-    double* up = vv + n;          // [NW][n]
-    __shared__ double xp[32];     // x / ls
+    __shared__ double xp[32];
     constexpr int kGradThreads = NW * 64, kGroups = kGradThreads / 32;
     __shared__ double red[kGradThreads];
     __shared__ double ga[kGroups][32], gu[kGroups][32];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    if (tid < 32) xp[tid] = tid < d ? x[(size_t)b * d + tid] / ls[tid] : 0.0;
-    __syncthreads();
-
-    // k*, c and mu_n partials
-    double mu_part = 0.0;
-    for (int i = tid; i < n; i += kGradThreads) {
-        double r2 = 0.0;
-        for (int j = 0; j < d; ++j) {
-            const double t = xp[j] - xs[(size_t)i * dp + j];
-            r2 = fma(t, t, r2);
-        }
-        const double t = kSqrt5 * sqrt(r2);
-        const double e = exp(-t);
-        const double k = amp * ((1.0 + t + t * t * (1.0 / 3.0)) * e);
-        kk[i] = k;
-        cc[i] = (-5.0 / 3.0) * amp * (1.0 + t) * e;
-        mu_part = fma(k, alpha[i], mu_part);
-    }
-    for (int i = tid; i < NW * n; i += kGradThreads) up[i] = 0.0;
-    __syncthreads();
-
-    // v = W k* (rows per wave, lanes across the row), q = ||v||^2
-    double q_part = 0.0;
-    for (int r = wave; r < n; r += NW) {
-        double s = 0.0;
-        for (int c = lane; c <= r; c += 64) s = fma(W[(size_t)r * n + c], kk[c], s);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-        if (lane == 0) vv[r] = s;
-        q_part = fma(s, s, q_part);     // identical in every lane: count lane 0 only
-    }
-    if (lane != 0) q_part = 0.0;
-    __syncthreads();
-
-    // u = W^T v: wave w accumulates rows r = w (mod NW) into its own partial
-    double* uw = up + (size_t)wave * n;
-    for (int r = wave; r < n; r += NW) {
-        const double vr = vv[r];
-        for (int c = lane; c <= r; c += 64) uw[c] = fma(W[(size_t)r * n + c], vr, uw[c]);
-    }
-    __syncthreads();
-    for (int i = tid; i < n; i += kGradThreads) {
-        double u = up[i];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) u += up[(size_t)w * n + i];
-        up[i] = u;
-    }
-
-    // block sums of mu_n and q
-    red[tid] = mu_part;
-    __syncthreads();
-    for (int s = kGradThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double mu_n = red[0];
-    __syncthreads();
-    red[tid] = q_part;
-    __syncthreads();
-    for (int s = kGradThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double q = red[0];
-
-    // dk^T alpha and dk^T u per dimension: thread (grp, j) sums observations grp (mod kGroups)
-    {
-        const int j = tid & 31, grp = tid >> 5;
-        double sa = 0.0, su = 0.0;
-        if (j < d) {
-            for (int i = grp; i < n; i += kGroups) {
-                const double t = cc[i] * (xp[j] - xs[(size_t)i * dp + j]);
-                sa = fma(t, alpha[i], sa);
-                su = fma(t, up[i], su);
-            }
-        }
-        ga[grp][j] = sa;
-        gu[grp][j] = su;
-    }
-    __syncthreads();
-
+    const int b = blockIdx.x, tid = threadIdx.x;
+    double mu = 0.0, sd = 0.0, mu_g = 0.0, sd_g = 0.0;
+    mpo::posterior_grad<NW>(gm, n, d, x + (size_t)b * d, sm, xp, red, ga, gu, mu, sd, mu_g, sd_g);
     if (tid < d) {
-        const int j = tid;
-        double sa = 0.0, su = 0.0;
-        for (int grp = 0; grp < kGroups; ++grp) {
-            sa += ga[grp][j];
-            su += gu[grp][j];
-        }
-        const double inv_ls = 1.0 / ls[j];
-        double var = amp - q;
-        if (var < 0.0) var = 0.0;
-        const double sd_n = sqrt(var);
-        const double mu = y_std * mu_n + y_mean;
-        const double sd = sd_n * y_std;
-        const double mu_g = y_std * sa * inv_ls;
-        const double sd_g = sd_n > 0.0 ? -y_std * su * inv_ls / sd_n : 0.0;
-        const int a = acq[b];
         double fv, gv;
-        if (a == (int)MPO_ACQ_LCB) {
-            fv = mu - kappa * sd;
-            gv = mu_g - kappa * sd_g;
-        } else if (sd <= 0.0) {
-            fv = 0.0;
-            gv = 0.0;
-        } else {
-            const double improve = y_opt - xi - mu;
-            const double z = improve / sd;
-            const double cdf = ndtr(z), pdf = norm_pdf(z);
-            const double improve_g = (-mu_g * sd - sd_g * improve) / (sd * sd);
-            if (a == (int)MPO_ACQ_PI) {
-                fv = -cdf;
-                gv = -(improve_g * pdf);
-            } else {
-                const double cdf_g = improve_g * pdf;
-                const double pdf_g = -improve * cdf_g;
-                fv = -(improve * cdf + sd * pdf);
-                gv = -((-mu_g * cdf - pdf_g) + (sd_g * pdf + pdf_g));
-            }
-        }
-        g[(size_t)b * d + j] = gv;
-        if (j == 0) f[b] = fv;
+        mpo::acq_value_grad(acq[b], mu, sd, mu_g, sd_g, y_opt, xi, kappa, fv, gv);
+        g[(size_t)b * d + tid] = gv;
+        if (tid == 0) f[b] = fv;
     }
 }
 
@@ -2128,28 +1997,16 @@ int mpo_gp_ei_score(const MpoGpModel* model, const double* cand, int64_t m, doub
     MPO_GUARD_END
 }
 
-// The form mpo_gp_acq_grad launches for this model: *waves = 16 or 4 waves per point and
-// *lds its dynamic LDS bytes.  `who` (may be NULL: no message) names the entry point in
-// a refusal.  The one place the choice is made: the launch and mpo_gp_acq_grad_path
-// both ask here.
+// The form mpo_gp_acq_grad launches for this model (mpo::grad_plan, with acq_grad_kernel's
+// own static LDS): the launch and mpo_gp_acq_grad_path both ask here.
 static int acq_grad_plan(const char* who, const MpoGpModel* model, int* waves, size_t* lds) {
     if (!(model && model->n > 0 && model->d > 0 && model->d <= 32 && model->W)) {
         if (who) mpo::set_error("%s: model not prepared", who);
         return MPO_EINVAL;
     }
-    // dynamic LDS per point: 19 n doubles (16 waves) or 7 n (4 waves); the static
-    // part (reduction rows, gradient tiles) is read from each kernel's code object
     static const size_t st16 = mpo::static_lds_bytes(reinterpret_cast<const void*>(acq_grad_kernel<16>));
     static const size_t st4 = mpo::static_lds_bytes(reinterpret_cast<const void*>(acq_grad_kernel<4>));
-    const size_t lds16 = (size_t)19 * model->n * sizeof(double), lds4 = (size_t)7 * model->n * sizeof(double);
-    const bool wide = lds16 + st16 <= kMaxLds;
-    if (!wide && lds4 + st4 > kMaxLds) {
-        if (who) mpo::set_error("%s: n=%d too large", who, model->n);
-        return MPO_ENOTSUP;
-    }
-    *waves = wide ? 16 : 4;
-    *lds = wide ? lds16 : lds4;
-    return MPO_OK;
+    return mpo::grad_plan(who, model->n, st16, st4, waves, lds);
 }
 
 int mpo_gp_acq_grad_path(const MpoGpModel* model) {
@@ -2171,8 +2028,7 @@ int mpo_gp_acq_grad(const MpoGpModel* model, const double* x, int batch, const i
     auto kern = wide ? acq_grad_kernel<16> : acq_grad_kernel<4>;
     MPO_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, dim3(batch), dim3(wide ? 1024 : 256), lds, static_cast<hipStream_t>(stream),
-                       model->n, model->d, model->dp, model->amp, model->y_mean, model->y_std, model->xs, model->ls,
-                       model->alpha, model->W, x, acq, y_opt, xi, kappa, f, g);
+                       model->n, model->d, mpo::grad_model(*model), x, acq, y_opt, xi, kappa, f, g);
     MPO_LAUNCH_CHECK();
     return MPO_OK;
     MPO_GUARD_END
@@ -2182,17 +2038,10 @@ int mpo_gp_acq_grad_host(const MpoGpModel* model, const double* x_host, int batc
                          double y_opt, double xi, double kappa, double* f_host, double* g_host, void* stream) {
     MPO_GUARD_BEGIN
     MPO_CHECK_ARG(x_host && acq_host && f_host && g_host, "mpo_gp_acq_grad_host: null pointer");
-    mpo::StreamDeviceScope on_device(static_cast<hipStream_t>(stream));
-    void* xd = mpo::pinned_device_view(x_host);
-    void* ad = mpo::pinned_device_view(acq_host);
-    void* fd = mpo::pinned_device_view(f_host);
-    void* gd = mpo::pinned_device_view(g_host);
-    MPO_CHECK_ARG(xd && ad && fd && gd, "mpo_gp_acq_grad_host: buffers must be pinned host memory");
-    const int rc = mpo_gp_acq_grad(model, static_cast<const double*>(xd), batch, static_cast<const int32_t*>(ad), y_opt,
-                                   xi, kappa, static_cast<double*>(fd), static_cast<double*>(gd), stream);
-    if (rc != MPO_OK) return rc;
-    MPO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    return MPO_OK;
+    return mpo::pinned_round("mpo_gp_acq_grad_host", stream, x_host, acq_host, f_host, g_host, nullptr,
+                             [&](const double* x, const int32_t* acq, double* f, double* g, double*) -> int {
+        return mpo_gp_acq_grad(model, x, batch, acq, y_opt, xi, kappa, f, g, stream);
+    });
     MPO_GUARD_END
 }
 

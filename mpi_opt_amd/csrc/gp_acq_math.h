@@ -1,5 +1,6 @@
-// Device arithmetic shared by the acquisition kernels (gp.hip, gp_ps.hip): scipy's ndtr,
-// the normal pdf and the (value, index) order of the top-k lists.
+// Device arithmetic shared by the acquisition kernels (gp.hip, gp_ps.hip, gp_grad.h): scipy's
+// ndtr, the normal pdf and the (value, index) order of the top-k lists and of the samplers'
+// argmin (gp_joint.hip, gp_paths.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -12,7 +12,7 @@
 //                       identity (the bc_* steps of mpo_gp_prepare, gp.hip)
 //   joint_sample_kernel S[r][i] = mu[i] + y_std sum_{j<=i} Lc[i][j] Z[j][r] and the
 //                       per-workgroup (min, index) of every draw
-//   joint_argmin_kernel the workgroups' partials of a draw folded in order
+//   mpo::argmin_fold    the workgroups' partials of a draw folded in order (gp_paths.hip)
 // mp = m rounded up to 32, np = the model's np16.  Only the plain W of the model is
 // read, never wfrag: the same kernels serve a resident, a streamed, an appended and a
 // from_factor model.  Every sum runs in a fixed order given (m, n, s): the launch
@@ -21,6 +21,7 @@
 // f64 16x16x4 operands: A[m = lane & 15][k = lane >> 4], B[k = lane >> 4][n = lane & 15];
 // C/D: col = lane & 15, row = (lane >> 4) + 4 q.
 #include "mpo_internal.h"
+#include "gp_acq_math.h"
 
 #include <algorithm>
 #include <cmath>
@@ -29,7 +30,8 @@ namespace {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
-using mpo::matern52;   // the Matern of bc_kmat_kernel (mpo_internal.h)
+using mpo::lex_less;   // gp_acq_math.h
+using mpo::matern52;  // the Matern of bc_kmat_kernel (mpo_internal.h)
 
 constexpr int kPanel = 256;           // observations per K* panel / columns of V per workgroup
 constexpr int kKsLd = kPanel + 2;     // LDS row stride of the panel: 16 rows on 16 distinct bank pairs
@@ -184,10 +186,6 @@ __global__ __launch_bounds__(256) void joint_cov_kernel(const double* __restrict
     }
 }
 
-__device__ __forceinline__ bool lex_less(double v, long long i, double w, long long j) {
-    return v < w || (v == w && i < j);
-}
-
 // Workgroup (bx, by): rows i in [64 bx, 64 bx + 64) (one 16-row tile per wave), draws
 // r in [16 by, 16 by + 16).  S[r][i] = mu[i] + y_std sum_{j <= i} Lc[i][j] Z[j][r]: the
 // lower-triangular k-steps only (the upper triangle of Lc's diagonal blocks still holds
@@ -243,21 +241,6 @@ __global__ __launch_bounds__(256) void joint_sample_kernel(const double* __restr
         part_val[(size_t)r * gridDim.x + blockIdx.x] = bv;
         part_idx[(size_t)r * gridDim.x + blockIdx.x] = bi;
     }
-}
-
-// argmin[r]: the draw's nb workgroup partials folded in order (ties to the lowest index)
-__global__ void joint_argmin_kernel(const double* __restrict__ part_val, const long long* __restrict__ part_idx,
-                                    int s, int nb, long long* __restrict__ argmin) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= s) return;
-    double bv = part_val[(size_t)r * nb];
-    long long bi = part_idx[(size_t)r * nb];
-    for (int b = 1; b < nb; ++b) {
-        const double v = part_val[(size_t)r * nb + b];
-        const long long i = part_idx[(size_t)r * nb + b];
-        if (lex_less(v, i, bv, bi)) { bv = v; bi = i; }
-    }
-    argmin[r] = bi;
 }
 
 struct JointWs {
@@ -381,11 +364,8 @@ int mpo_gp_sample(const MpoGpModel* model, const double* cand, int m, const doub
     hipLaunchKernelGGL(joint_sample_kernel, dim3(nb, (s + 15) / 16), dim3(256), 0, st, w.A, mp, m, z, s, w.mu_n,
                        model->y_mean, model->y_std, samples, argmin ? w.part_val : nullptr, w.part_idx);
     MPO_LAUNCH_CHECK();
-    if (argmin) {
-        hipLaunchKernelGGL(joint_argmin_kernel, dim3((s + 255) / 256), dim3(256), 0, st, w.part_val, w.part_idx, s, nb,
-                           reinterpret_cast<long long*>(argmin));
-        MPO_LAUNCH_CHECK();
-    }
+    if (argmin)
+        MPO_HIP(mpo::argmin_fold(w.part_val, w.part_idx, s, nb, reinterpret_cast<long long*>(argmin), nullptr, st));
     return MPO_OK;
     MPO_GUARD_END
 }

@@ -13,7 +13,7 @@
 //   paths_coef_kernel    coef = [scale w ; 0 ; alpha - W^T t ; 0]                [Kp][sp]
 //   paths_eval_kernel    f_r(x) = y_mean + y_std (A(x) coef[:, r]),  A = [phi | amp Matern52(|c - xs|)],
 //                        the optional sample rows and the per-workgroup (min, index) of every draw
-//   paths_argmin_kernel  the workgroups' partials of a draw folded in order
+//   argmin_fold_kernel   the workgroups' partials of a draw folded in order (mpo::argmin_fold)
 //   paths_grad_kernel    f_r(x) and its gradient at one point per workgroup (mpo_gp_paths_grad: the
 //                        objective of a continuous minimisation of a draw; no MFMA, latency-bound)
 // Fp = F rounded up to 16, Kp = Fp + np16 rounded up to 64 (the K panel), sp = s rounded up
@@ -26,6 +26,7 @@
 // f64 16x16x4 operands: A[m = lane & 15][k = lane >> 4], B[k = lane >> 4][n = lane & 15];
 // C/D: col = lane & 15, row = (lane >> 4) + 4 q.
 #include "mpo_internal.h"
+#include "gp_acq_math.h"
 
 #include <algorithm>
 #include <cmath>
@@ -35,6 +36,7 @@ namespace {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
+using mpo::lex_less;   // gp_acq_math.h
 using mpo::matern52;   // the Matern of bc_kmat_kernel (mpo_internal.h)
 
 constexpr int kTileM = 64;            // candidates per tile: four 16-row MFMA tiles
@@ -116,10 +118,6 @@ __global__ void paths_coef_kernel(const double* __restrict__ W, const double* __
 }
 
 // ---- eval --------------------------------------------------------------------------------
-
-__device__ __forceinline__ bool lex_less(double v, long long i, double w, long long j) {
-    return v < w || (v == w && i < j);
-}
 
 // Workgroup (bx, by): the candidate tiles bx, bx + gridDim.x, .. of 64 rows, the draws
 // first + 256 by .. of the call (16-draw tiles; wave w owns tiles w, w + 4, w + 8, w + 12 and
@@ -272,7 +270,7 @@ __global__ __launch_bounds__(256, 2) void paths_eval_kernel(
 }
 
 // argmin[r] / minval[r]: the draw's nb workgroup partials folded in order (ties to the lowest index)
-__global__ void paths_argmin_kernel(const double* __restrict__ part_val, const long long* __restrict__ part_idx,
+__global__ void argmin_fold_kernel(const double* __restrict__ part_val, const long long* __restrict__ part_idx,
                                     int n_draws, int nb, long long* __restrict__ argmin, double* __restrict__ minval) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_draws) return;
@@ -452,6 +450,13 @@ GradKernel pick_grad_kernel(int dp) {
 
 }  // namespace
 
+hipError_t mpo::argmin_fold(const double* part_val, const long long* part_idx, int n_draws, int nb, long long* argmin,
+                            double* minval, hipStream_t s) {
+    hipLaunchKernelGGL(argmin_fold_kernel, dim3((n_draws + 255) / 256), dim3(256), 0, s, part_val, part_idx, n_draws, nb,
+                       argmin, minval);
+    return hipGetLastError();
+}
+
 extern "C" {
 
 size_t mpo_gp_paths_ws_bytes(const MpoGpModel* model, int F, int s) {
@@ -556,11 +561,7 @@ int mpo_gp_paths_eval(const MpoGpModel* model, const MpoGpPaths* paths, const do
                        paths->Fp, paths->Kp, paths->coef, paths->sp, first_draw, n_draws, model->y_mean, model->y_std,
                        samples, fold ? part_val : nullptr, part_idx, eval_tiles(m));
     MPO_LAUNCH_CHECK();
-    if (fold) {
-        hipLaunchKernelGGL(paths_argmin_kernel, dim3((n_draws + 255) / 256), dim3(256), 0, st, part_val, part_idx,
-                           n_draws, gx, reinterpret_cast<long long*>(argmin), minval);
-        MPO_LAUNCH_CHECK();
-    }
+    if (fold) MPO_HIP(mpo::argmin_fold(part_val, part_idx, n_draws, gx, reinterpret_cast<long long*>(argmin), minval, st));
     return MPO_OK;
     MPO_GUARD_END
 }
@@ -595,20 +596,13 @@ int mpo_gp_paths_grad_host(const MpoGpModel* model, const MpoGpPaths* paths, con
     MPO_GUARD_BEGIN
     const char* who = "mpo_gp_paths_grad_host";
     if (const int rc = paths_grad_check(who, model, paths, x_host, draw_host, batch, f_host, g_host)) return rc;
-    mpo::StreamDeviceScope on_device(static_cast<hipStream_t>(stream));
-    void* xd = mpo::pinned_device_view(x_host);
-    void* dd = mpo::pinned_device_view(draw_host);
-    void* fd = mpo::pinned_device_view(f_host);
-    void* gd = mpo::pinned_device_view(g_host);
-    MPO_CHECK_ARG(xd && dd && fd && gd, "%s: buffers must be pinned host memory", who);
-    for (int b = 0; b < batch; ++b)
-        MPO_CHECK_ARG(draw_host[b] >= 0 && draw_host[b] < paths->s, "%s: draw[%d]=%d outside [0, %d)", who, b,
-                      draw_host[b], paths->s);
-    const int rc = mpo_gp_paths_grad(model, paths, static_cast<const double*>(xd), static_cast<const int32_t*>(dd),
-                                     batch, static_cast<double*>(fd), static_cast<double*>(gd), stream);
-    if (rc != MPO_OK) return rc;
-    MPO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    return MPO_OK;
+    return mpo::pinned_round(who, stream, x_host, draw_host, f_host, g_host, nullptr,
+                             [&](const double* x, const int32_t* draw, double* f, double* g, double*) -> int {
+        for (int b = 0; b < batch; ++b)
+            MPO_CHECK_ARG(draw_host[b] >= 0 && draw_host[b] < paths->s, "%s: draw[%d]=%d outside [0, %d)", who, b,
+                          draw_host[b], paths->s);
+        return mpo_gp_paths_grad(model, paths, x, draw, batch, f, g, stream);
+    });
     MPO_GUARD_END
 }
 

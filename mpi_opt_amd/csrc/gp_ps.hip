@@ -12,22 +12,22 @@
 //   ps_finish_kernel    the elementwise product over m candidates after the two models'
 //                       own scoring passes, and per-wave top-k lists
 //   acq_ps_grad_kernel  value + gradient at a few points (the polish objective): both
-//                       posteriors and their gradients in one launch, one workgroup per point
+//                       posteriors and their gradients (mpo::posterior_grad, gp_grad.h) in
+//                       one launch, one workgroup per point
 
-#include "mpo_internal.h"
-#include "gp_acq_math.h"
+#include "gp_grad.h"
 
 #include <algorithm>
 
 namespace {
 
-using mpo::kSqrt5;
+using mpo::acq_value_grad;
+using mpo::grad_model;
+using mpo::GradModel;
 using mpo::lex_less;
-using mpo::ndtr;
-using mpo::norm_pdf;
+using mpo::posterior_grad;
 using mpo::wave_lex_min;
 
-constexpr size_t kMaxLds = 160 * 1024;
 constexpr unsigned kPsFlags = MPO_ACQ_EI | MPO_ACQ_PI;
 
 // E[1/t] of a log-normal t with log t ~ N(mu, s^2).  One place: the scoring finish and the
@@ -124,135 +124,6 @@ __global__ __launch_bounds__(kFinThreads) void ps_finish_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// What the polish kernel reads of one prepared model.
-struct GradModel {
-    double amp, y_mean, y_std;
-    const double* xs;
-    const double* ls;
-    const double* alpha;
-    const double* W;
-    int dp;
-};
-
-inline GradModel grad_model(const MpoGpModel& m) {
-    return GradModel{m.amp, m.y_mean, m.y_std, m.xs, m.ls, m.alpha, m.W, m.dp};
-}
-
-// Posterior and its gradient at the point x [d] under one model, by the whole workgroup:
-// the sequence of acq_grad_kernel (gp.hip) -- k*, c, v = W k*, u = W^T v, dk^T alpha,
-// dk^T u -- with the same thread-to-term maps, so every sum runs in that kernel's order.
-// Threads j < d leave with mu, sd and their component of grad mu, grad sd.  Ends behind a
-// barrier: the LDS is free for the next model.
-template <int NW>
-__device__ __forceinline__ void posterior_grad(const GradModel& gm, int n, int d, const double* __restrict__ x,
-                                               double* sm, double* xp, double* red, double (*ga)[32],
-                                               double (*gu)[32], double& mu, double& sd, double& mu_g, double& sd_g) {
-    constexpr int kGradThreads = NW * 64, kGroups = kGradThreads / 32;
-    double* kk = sm;              // [n]
-    double* cc = kk + n;          // [n]
-    double* vv = cc + n;          // [n]
-    double* up = vv + n;          // [NW][n]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const double amp = gm.amp;
-    const double* __restrict__ xs = gm.xs;
-    const double* __restrict__ alpha = gm.alpha;
-    const double* __restrict__ W = gm.W;
-    const int dp = gm.dp;
-    if (tid < 32) xp[tid] = tid < d ? x[tid] / gm.ls[tid] : 0.0;
-    __syncthreads();
-
-    double mu_part = 0.0;
-    for (int i = tid; i < n; i += kGradThreads) {
-        double r2 = 0.0;
-        for (int j = 0; j < d; ++j) {
-            const double t = xp[j] - xs[(size_t)i * dp + j];
-            r2 = fma(t, t, r2);
-        }
-        const double t = kSqrt5 * sqrt(r2);
-        const double e = exp(-t);
-        const double k = amp * ((1.0 + t + t * t * (1.0 / 3.0)) * e);
-        kk[i] = k;
-        cc[i] = (-5.0 / 3.0) * amp * (1.0 + t) * e;
-        mu_part = fma(k, alpha[i], mu_part);
-    }
-    for (int i = tid; i < NW * n; i += kGradThreads) up[i] = 0.0;
-    __syncthreads();
-
-    double q_part = 0.0;
-    for (int r = wave; r < n; r += NW) {
-        double s = 0.0;
-        for (int c = lane; c <= r; c += 64) s = fma(W[(size_t)r * n + c], kk[c], s);
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-        if (lane == 0) vv[r] = s;
-        q_part = fma(s, s, q_part);
-    }
-    if (lane != 0) q_part = 0.0;
-    __syncthreads();
-
-    double* uw = up + (size_t)wave * n;
-    for (int r = wave; r < n; r += NW) {
-        const double vr = vv[r];
-        for (int c = lane; c <= r; c += 64) uw[c] = fma(W[(size_t)r * n + c], vr, uw[c]);
-    }
-    __syncthreads();
-    for (int i = tid; i < n; i += kGradThreads) {
-        double u = up[i];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) u += up[(size_t)w * n + i];
-        up[i] = u;
-    }
-
-    red[tid] = mu_part;
-    __syncthreads();
-    for (int s = kGradThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double mu_n = red[0];
-    __syncthreads();
-    red[tid] = q_part;
-    __syncthreads();
-    for (int s = kGradThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double q = red[0];
-
-    {
-        const int j = tid & 31, grp = tid >> 5;
-        double sa = 0.0, su = 0.0;
-        if (j < d) {
-            for (int i = grp; i < n; i += kGroups) {
-                const double t = cc[i] * (xp[j] - xs[(size_t)i * dp + j]);
-                sa = fma(t, alpha[i], sa);
-                su = fma(t, up[i], su);
-            }
-        }
-        ga[grp][j] = sa;
-        gu[grp][j] = su;
-    }
-    __syncthreads();
-
-    if (tid < d) {
-        const int j = tid;
-        double sa = 0.0, su = 0.0;
-        for (int grp = 0; grp < kGroups; ++grp) {
-            sa += ga[grp][j];
-            su += gu[grp][j];
-        }
-        const double inv_ls = 1.0 / gm.ls[j];
-        double var = amp - q;
-        if (var < 0.0) var = 0.0;
-        const double sd_n = sqrt(var);
-        mu = gm.y_std * mu_n + gm.y_mean;
-        sd = sd_n * gm.y_std;
-        mu_g = gm.y_std * sa * inv_ls;
-        sd_g = sd_n > 0.0 ? -gm.y_std * su * inv_ls / sd_n : 0.0;
-    }
-    __syncthreads();
-}
-
 // One workgroup per point b: f[b] = v, g[b][d] = grad v of acquisition acq[b] (MPO_ACQ_EI or
 // MPO_ACQ_PI; anything else gives NaN), parts[b] = (a, inv_t, mu_t, s_t) when parts is set.
 // LDS as acq_grad_kernel: (3 + NW) n doubles, used by one model after the other.
@@ -275,25 +146,8 @@ __global__ __launch_bounds__(NW * 64) void acq_ps_grad_kernel(
 
     if (tid < d) {
         const int a = acq[b];
-        double av, ag;     // the plain acquisition: mpo_gp_acq_grad's arithmetic
-        if (sd <= 0.0) {
-            av = 0.0;
-            ag = 0.0;
-        } else {
-            const double improve = y_opt - xi - mu;
-            const double z = improve / sd;
-            const double cdf = ndtr(z), pdf = norm_pdf(z);
-            const double improve_g = (-mu_g * sd - sd_g * improve) / (sd * sd);
-            if (a == (int)MPO_ACQ_PI) {
-                av = -cdf;
-                ag = -(improve_g * pdf);
-            } else {
-                const double cdf_g = improve_g * pdf;
-                const double pdf_g = -improve * cdf_g;
-                av = -(improve * cdf + sd * pdf);
-                ag = -((-mu_g * cdf - pdf_g) + (sd_g * pdf + pdf_g));
-            }
-        }
+        double av, ag;     // the plain acquisition, as mpo_gp_acq_grad computes it
+        acq_value_grad(a, mu, sd, mu_g, sd_g, y_opt, xi, 0.0, av, ag);
         if (a != (int)MPO_ACQ_EI && a != (int)MPO_ACQ_PI) av = ag = __builtin_nan("");
         const double it = inv_time(mt, st);
         const double v = av * it;
@@ -366,20 +220,12 @@ bool carve_ps_ws(void* ws, const MpoGpModel* fm, const MpoGpModel* tm, int64_t m
     return true;
 }
 
-// The form of acq_ps_grad_kernel for n observations: 16 waves per point while its LDS fits,
-// 4 past it (the rule of mpo_gp_acq_grad, with this kernel's own static LDS).
+// The form of acq_ps_grad_kernel for n observations (mpo::grad_plan, with this kernel's own
+// static LDS).
 int ps_grad_plan(const char* who, int n, int* waves, size_t* lds) {
     static const size_t st16 = mpo::static_lds_bytes(reinterpret_cast<const void*>(acq_ps_grad_kernel<16>));
     static const size_t st4 = mpo::static_lds_bytes(reinterpret_cast<const void*>(acq_ps_grad_kernel<4>));
-    const size_t lds16 = (size_t)19 * n * sizeof(double), lds4 = (size_t)7 * n * sizeof(double);
-    const bool wide = lds16 + st16 <= kMaxLds;
-    if (!wide && lds4 + st4 > kMaxLds) {
-        if (who) mpo::set_error("%s: n=%d too large", who, n);
-        return MPO_ENOTSUP;
-    }
-    *waves = wide ? 16 : 4;
-    *lds = wide ? lds16 : lds4;
-    return MPO_OK;
+    return mpo::grad_plan(who, n, st16, st4, waves, lds);
 }
 
 }  // namespace
@@ -469,22 +315,13 @@ int mpo_gp_acq_ps_grad_host(const MpoGpModel* fmodel, const MpoGpModel* tmodel, 
     if (!pair_ok(who, fmodel, tmodel)) return MPO_EINVAL;
     MPO_CHECK_ARG(x_host && acq_host && f_host && g_host, "%s: null pointer", who);
     MPO_CHECK_ARG(batch > 0 && batch <= 65535, "%s: batch=%d outside [1, 65535]", who, batch);
-    mpo::StreamDeviceScope on_device(static_cast<hipStream_t>(stream));
-    void* xd = mpo::pinned_device_view(x_host);
-    void* ad = mpo::pinned_device_view(acq_host);
-    void* fd = mpo::pinned_device_view(f_host);
-    void* gd = mpo::pinned_device_view(g_host);
-    void* pd = parts_host ? mpo::pinned_device_view(parts_host) : nullptr;
-    MPO_CHECK_ARG(xd && ad && fd && gd && (pd || !parts_host), "%s: buffers must be pinned host memory", who);
-    for (int b = 0; b < batch; ++b)
-        MPO_CHECK_ARG(acq_host[b] == (int32_t)MPO_ACQ_EI || acq_host[b] == (int32_t)MPO_ACQ_PI,
-                      "%s: acq[%d]=%d is neither MPO_ACQ_EI nor MPO_ACQ_PI", who, b, acq_host[b]);
-    const int rc = mpo_gp_acq_ps_grad(fmodel, tmodel, static_cast<const double*>(xd), batch,
-                                      static_cast<const int32_t*>(ad), y_opt, xi, static_cast<double*>(fd),
-                                      static_cast<double*>(gd), static_cast<double*>(pd), stream);
-    if (rc != MPO_OK) return rc;
-    MPO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    return MPO_OK;
+    return mpo::pinned_round(who, stream, x_host, acq_host, f_host, g_host, parts_host,
+                             [&](const double* x, const int32_t* acq, double* f, double* g, double* parts) -> int {
+        for (int b = 0; b < batch; ++b)
+            MPO_CHECK_ARG(acq_host[b] == (int32_t)MPO_ACQ_EI || acq_host[b] == (int32_t)MPO_ACQ_PI,
+                          "%s: acq[%d]=%d is neither MPO_ACQ_EI nor MPO_ACQ_PI", who, b, acq_host[b]);
+        return mpo_gp_acq_ps_grad(fmodel, tmodel, x, batch, acq, y_opt, xi, f, g, parts, stream);
+    });
     MPO_GUARD_END
 }
 

@@ -1089,6 +1089,26 @@ Options to_options(const MpoLbfgsbOptions* o) {
     return Options{o->ftol, o->gtol, o->maxiter, o->maxfun, o->maxcor, o->maxls};
 }
 
+// The polishes (mpo_gp_polish_host and its kin): drive() on an objective that is evaluated in
+// place on pinned host buffers.  One round copies the live runs' points to x_host and their
+// ids (ids_src[run]: acquisition codes or draws) to id_host, calls objective(batch), which
+// fills f_host / g_host, and copies those back.
+template <class Objective>
+int polish_drive(int d, int nruns, const double* starts, const double* bounds, const MpoLbfgsbOptions* opts,
+                 const int32_t* ids_src, double* x_host, int32_t* id_host, double* f_host, double* g_host,
+                 double* x_out, double* f_out, int32_t* stats, int32_t* rounds, Objective&& objective) {
+    auto eval = [&](int b, const double* Xp, const int32_t* ids, double* f, double* g) -> int {
+        std::memcpy(x_host, Xp, sizeof(double) * (size_t)b * d);
+        for (int i = 0; i < b; ++i) id_host[i] = ids_src[ids[i]];
+        const int rc = objective(b);
+        if (rc != MPO_OK) return rc;
+        std::memcpy(f, f_host, sizeof(double) * b);
+        std::memcpy(g, g_host, sizeof(double) * (size_t)b * d);
+        return 0;
+    };
+    return drive(d, nruns, starts, bounds, to_options(opts), eval, x_out, f_out, stats, rounds);
+}
+
 // Rendezvous of the concurrent refits on one device (the cl_min chains' worker
 // threads).  A fit registers for its duration; each of its rounds is queued, and
 // the first thread that finds every registered fit either queued or already in a
@@ -1305,18 +1325,11 @@ int mpo_gp_polish_host(const MpoGpModel* model, const double* starts, const int3
     MPO_GUARD_BEGIN
     MPO_CHECK_ARG(model && acq && x_host && acq_host && f_host && g_host && x_out && f_out,
                   "mpo_gp_polish_host: null pointer");
-    const int d = model->d;
-    MPO_CHECK_ARG(options_ok(d, nruns, starts, bounds, opts), "mpo_gp_polish_host: bad options / bounds");
-    auto eval = [&](int b, const double* Xp, const int32_t* ids, double* f, double* g) -> int {
-        std::memcpy(x_host, Xp, sizeof(double) * (size_t)b * d);
-        for (int i = 0; i < b; ++i) acq_host[i] = acq[ids[i]];
-        const int rc = mpo_gp_acq_grad_host(model, x_host, b, acq_host, y_opt, xi, kappa, f_host, g_host, stream);
-        if (rc != MPO_OK) return rc;
-        std::memcpy(f, f_host, sizeof(double) * b);
-        std::memcpy(g, g_host, sizeof(double) * (size_t)b * d);
-        return 0;
-    };
-    return drive(d, nruns, starts, bounds, to_options(opts), eval, x_out, f_out, stats, rounds);
+    MPO_CHECK_ARG(options_ok(model->d, nruns, starts, bounds, opts), "mpo_gp_polish_host: bad options / bounds");
+    return polish_drive(model->d, nruns, starts, bounds, opts, acq, x_host, acq_host, f_host, g_host, x_out, f_out,
+                        stats, rounds, [&](int b) {
+        return mpo_gp_acq_grad_host(model, x_host, b, acq_host, y_opt, xi, kappa, f_host, g_host, stream);
+    });
     MPO_GUARD_END
 }
 
@@ -1327,19 +1340,11 @@ int mpo_gp_polish_ps_host(const MpoGpModel* fmodel, const MpoGpModel* tmodel, co
     MPO_GUARD_BEGIN
     MPO_CHECK_ARG(fmodel && tmodel && acq && x_host && acq_host && f_host && g_host && x_out && f_out,
                   "mpo_gp_polish_ps_host: null pointer");
-    const int d = fmodel->d;
-    MPO_CHECK_ARG(options_ok(d, nruns, starts, bounds, opts), "mpo_gp_polish_ps_host: bad options / bounds");
-    auto eval = [&](int b, const double* Xp, const int32_t* ids, double* f, double* g) -> int {
-        std::memcpy(x_host, Xp, sizeof(double) * (size_t)b * d);
-        for (int i = 0; i < b; ++i) acq_host[i] = acq[ids[i]];
-        const int rc = mpo_gp_acq_ps_grad_host(fmodel, tmodel, x_host, b, acq_host, y_opt, xi, f_host, g_host, nullptr,
-                                               stream);
-        if (rc != MPO_OK) return rc;
-        std::memcpy(f, f_host, sizeof(double) * b);
-        std::memcpy(g, g_host, sizeof(double) * (size_t)b * d);
-        return 0;
-    };
-    return drive(d, nruns, starts, bounds, to_options(opts), eval, x_out, f_out, stats, rounds);
+    MPO_CHECK_ARG(options_ok(fmodel->d, nruns, starts, bounds, opts), "mpo_gp_polish_ps_host: bad options / bounds");
+    return polish_drive(fmodel->d, nruns, starts, bounds, opts, acq, x_host, acq_host, f_host, g_host, x_out, f_out,
+                        stats, rounds, [&](int b) {
+        return mpo_gp_acq_ps_grad_host(fmodel, tmodel, x_host, b, acq_host, y_opt, xi, f_host, g_host, nullptr, stream);
+    });
     MPO_GUARD_END
 }
 
@@ -1350,20 +1355,13 @@ int mpo_gp_paths_polish_host(const MpoGpModel* model, const MpoGpPaths* paths, c
     MPO_GUARD_BEGIN
     MPO_CHECK_ARG(model && paths && draw && x_host && draw_host && f_host && g_host && x_out && f_out,
                   "mpo_gp_paths_polish_host: null pointer");
-    const int d = model->d;
-    MPO_CHECK_ARG(options_ok(d, nruns, starts, bounds, opts), "mpo_gp_paths_polish_host: bad options / bounds");
+    MPO_CHECK_ARG(options_ok(model->d, nruns, starts, bounds, opts), "mpo_gp_paths_polish_host: bad options / bounds");
     MPO_CHECK_ARG(nruns <= MPO_PATHS_GRAD_BMAX, "mpo_gp_paths_polish_host: nruns=%d exceeds %d", nruns,
                   MPO_PATHS_GRAD_BMAX);
-    auto eval = [&](int b, const double* Xp, const int32_t* ids, double* f, double* g) -> int {
-        std::memcpy(x_host, Xp, sizeof(double) * (size_t)b * d);
-        for (int i = 0; i < b; ++i) draw_host[i] = draw[ids[i]];
-        const int rc = mpo_gp_paths_grad_host(model, paths, x_host, draw_host, b, f_host, g_host, stream);
-        if (rc != MPO_OK) return rc;
-        std::memcpy(f, f_host, sizeof(double) * b);
-        std::memcpy(g, g_host, sizeof(double) * (size_t)b * d);
-        return 0;
-    };
-    return drive(d, nruns, starts, bounds, to_options(opts), eval, x_out, f_out, stats, rounds);
+    return polish_drive(model->d, nruns, starts, bounds, opts, draw, x_host, draw_host, f_host, g_host, x_out, f_out,
+                        stats, rounds, [&](int b) {
+        return mpo_gp_paths_grad_host(model, paths, x_host, draw_host, b, f_host, g_host, stream);
+    });
     MPO_GUARD_END
 }
 

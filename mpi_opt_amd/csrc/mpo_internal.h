@@ -26,6 +26,9 @@ constexpr int kMaxObs = 2048;
 
 constexpr double kSqrt5 = 2.236067977499789696409173668731276235;
 
+// LDS a workgroup may use (gfx950: 160 KiB per CU)
+constexpr size_t kMaxLds = 160 * 1024;
+
 // sklearn kernels.py:1715-1724 (nu = 2.5) times ConstantKernel: the factorisation's and the
 // joint posterior's Matern (gp.hip, gp_joint.hip).
 __device__ __forceinline__ double matern52(double r, double amp) {
@@ -214,6 +217,13 @@ constexpr int kTopkMergeGroups = 256;
 hipError_t topk_merge(const long long* part_idx, const double* part_val, int nparts, int k, unsigned flags,
                       long long* mid_idx, double* mid_val, long long* out_idx, double* out_val, hipStream_t s);
 
+// The samplers' argmin fold (gp_paths.hip: argmin_fold_kernel; gp_joint.hip folds with it
+// too): argmin[r] / minval[r] (either may be null) of draw r < n_draws from its nb
+// workgroup partials part_val / part_idx [r * nb + b], folded in order, ties to the lowest
+// index.
+hipError_t argmin_fold(const double* part_val, const long long* part_idx, int n_draws, int nb, long long* argmin,
+                       double* minval, hipStream_t s);
+
 }  // namespace mpo
 
 #define MPO_CHECK_ARG(cond, ...)              \
@@ -243,3 +253,28 @@ hipError_t topk_merge(const long long* part_idx, const double* part_val, int npa
         ::mpo::set_error("unexpected C++ exception");         \
         return MPO_EHIP;                                      \
     }
+
+namespace mpo {
+
+// One round of a polish objective on pinned host buffers (mpo_gp_acq_grad_host and its kin):
+// makes the stream's device current, resolves x, ids, f, g and the optional `extra` to the
+// device views a kernel reads and writes in place, runs launch(xd, idd, fd, gd, extrad) --
+// the objective's own host-side checks and its enqueue -- and synchronises the stream.
+template <class Launch>
+int pinned_round(const char* who, void* stream, const double* x, const int32_t* ids, double* f, double* g,
+                 double* extra, Launch&& launch) {
+    StreamDeviceScope on_device(static_cast<hipStream_t>(stream));
+    void* xd = pinned_device_view(x);
+    void* id = pinned_device_view(ids);
+    void* fd = pinned_device_view(f);
+    void* gd = pinned_device_view(g);
+    void* ed = extra ? pinned_device_view(extra) : nullptr;
+    MPO_CHECK_ARG(xd && id && fd && gd && (ed || !extra), "%s: buffers must be pinned host memory", who);
+    const int rc = launch(static_cast<const double*>(xd), static_cast<const int32_t*>(id), static_cast<double*>(fd),
+                          static_cast<double*>(gd), static_cast<double*>(ed));
+    if (rc != MPO_OK) return rc;
+    MPO_HIP(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
+    return MPO_OK;
+}
+
+}  // namespace mpo

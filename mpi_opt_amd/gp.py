@@ -239,19 +239,11 @@ class DeviceGP:
         return mu, sd, ei, am
 
     def _ensure_ag(self, B):
-        """Pinned host buffers of one polish round (x, acquisition codes, f, g) for B points."""
-        if getattr(self, "_ag_cap", 0) < B:
-            cap = max(16, B)
-            d = self.d
-            self._ag_x = torch.empty(cap * d, dtype=torch.float64).pin_memory()
-            self._ag_a = torch.empty(cap, dtype=torch.int32).pin_memory()
-            self._ag_f = torch.empty(cap, dtype=torch.float64).pin_memory()
-            self._ag_g = torch.empty(cap * d, dtype=torch.float64).pin_memory()
-            self._ag_np = (self._ag_x.numpy(), self._ag_a.numpy(), self._ag_f.numpy(), self._ag_g.numpy())
-            self._ag_ptrs = (self._ag_x.data_ptr(), self._ag_a.data_ptr(), self._ag_f.data_ptr(),
-                             self._ag_g.data_ptr())
+        """The pinned buffers of one polish round (x, acquisition codes, f, g) for B points."""
+        if getattr(self, "_ag", None) is None:
+            self._ag = PinnedRound(self.d)
             self._ag_stream = _lib.stream_handle(self.device)
-            self._ag_cap = cap
+        return self._ag.ensure(B)
 
     @property
     def acq_grad_path(self):
@@ -268,44 +260,24 @@ class DeviceGP:
         host memory and writes f, g into it (no staging copies: a polish round is
         ~30 us of device time, torch's copies and stream context cost as much);
         returns numpy (f (B,), g (B, d))."""
-        X = np.asarray(X, dtype=np.float64).reshape(-1, self.d)
-        B, d = X.shape
-        self._ensure_ag(B)
-        xn, an, fn, gn = self._ag_np
-        xn[:B * d] = X.reshape(-1)
-        an[:B] = acq_codes
-        xp, ap, fp, gp = self._ag_ptrs
+        r, B = _stage_round(self, X, acq_codes)
+        xp, ap, fp, gp = r.ptrs
         rc = lib().mpo_gp_acq_grad_host(ctypes.byref(self.model), xp, B, ap, float(y_opt), float(xi), float(kappa),
                                         fp, gp, self._ag_stream)
         if rc != 0:
             check(rc, "mpo_gp_acq_grad_host")
-        return fn[:B].copy(), gn[:B * d].reshape(B, d).copy()
+        return r.fg(B)
 
     def polish(self, starts, acq_codes, y_opt, xi, kappa, bounds, ftol, maxiter=20, gtol=1e-5, maxfun=15000):
         """skopt's polish of its best candidates, whole, in ``mpo_gp_polish_host``:
         L-BFGS-B (libmpo.so's host driver) from each row of ``starts`` (B, d) on
         acquisition ``acq_codes[r]``, one ``mpo_gp_acq_grad_host`` round per
         iteration of all live runs.  Returns [(x, f)] per run."""
-        starts = np.ascontiguousarray(np.asarray(starts, dtype=np.float64))
-        B, d = starts.shape
-        if d != self.d:
-            raise ValueError(f"polish starts must be (B, {self.d}), got {starts.shape}")
-        self._ensure_ag(B)
-        codes = np.ascontiguousarray(np.asarray(acq_codes, dtype=np.int32))
-        b = np.ascontiguousarray(np.asarray(bounds, dtype=np.float64).reshape(d, 2))
-        opts = _lib.MpoLbfgsbOptions(ftol, gtol, maxiter, maxfun, 10, 20)
-        x = np.empty((B, d))
-        f = np.empty(B)
-        stats = np.empty((B, 4), np.int32)
-        rounds = ctypes.c_int32(0)
-        xp, ap, fp, gp = self._ag_ptrs
-        rc = lib().mpo_gp_polish_host(ctypes.byref(self.model), starts.ctypes.data, codes.ctypes.data, B,
-                                      b.ctypes.data, ctypes.byref(opts), float(y_opt), float(xi), float(kappa),
-                                      xp, ap, fp, gp, x.ctypes.data, f.ctypes.data, stats.ctypes.data,
-                                      ctypes.byref(rounds), self._ag_stream)
-        if rc != 0:
-            check(rc, "mpo_gp_polish_host")
-        return [(x[r], float(f[r])) for r in range(B)]
+        starts = _polish_starts(starts, self.d)
+        x, f, _, _ = _run_polish("mpo_gp_polish_host", (ctypes.byref(self.model),),
+                                 (float(y_opt), float(xi), float(kappa)), starts, acq_codes, bounds, ftol, maxiter,
+                                 gtol, maxfun, self._ensure_ag(len(starts)), self._ag_stream)
+        return [(x[r], float(f[r])) for r in range(len(starts))]
 
     # -- joint posterior -------------------------------------------------------
     def _ensure_joint_ws(self, m, s):
@@ -440,13 +412,8 @@ def acq_grad_ps(fgp, tgp, X, acq_codes, y_opt, xi=0.01, want_parts=False):
     pinned round buffers.  Returns numpy ``(f (B,), g (B, d))``, with ``want_parts`` also
     ``parts (B, 4) = (a, inv_t, mu_t, s_t)``."""
     _check_pair(fgp, tgp)
-    X = np.asarray(X, dtype=np.float64).reshape(-1, fgp.d)
-    B, d = X.shape
-    fgp._ensure_ag(B)
-    xn, an, fn, gn = fgp._ag_np
-    xn[:B * d] = X.reshape(-1)
-    an[:B] = acq_codes
-    xp, ap, fp, gp = fgp._ag_ptrs
+    r, B = _stage_round(fgp, X, acq_codes)
+    xp, ap, fp, gp = r.ptrs
     parts = None
     if want_parts:
         if getattr(fgp, "_ag_parts", None) is None or fgp._ag_parts.numel() < 4 * B:
@@ -456,36 +423,85 @@ def acq_grad_ps(fgp, tgp, X, acq_codes, y_opt, xi=0.01, want_parts=False):
                                        float(xi), fp, gp, ptr(parts), fgp._ag_stream)
     if rc != 0:
         check(rc, "mpo_gp_acq_ps_grad_host")
-    f, g = fn[:B].copy(), gn[:B * d].reshape(B, d).copy()
     if want_parts:
-        return f, g, parts.numpy()[:4 * B].reshape(B, 4).copy()
-    return f, g
+        return r.fg(B) + (parts.numpy()[:4 * B].reshape(B, 4).copy(),)
+    return r.fg(B)
 
 
 def polish_ps(fgp, tgp, starts, acq_codes, y_opt, xi, bounds, ftol, maxiter=20, gtol=1e-5, maxfun=15000):
     """``mpo_gp_polish_ps_host``: :meth:`DeviceGP.polish` on the cost-aware objective.
     Returns [(x, f)] per run."""
     _check_pair(fgp, tgp)
+    starts = _polish_starts(starts, fgp.d)
+    x, f, _, _ = _run_polish("mpo_gp_polish_ps_host", (ctypes.byref(fgp.model), ctypes.byref(tgp.model)),
+                             (float(y_opt), float(xi)), starts, acq_codes, bounds, ftol, maxiter, gtol, maxfun,
+                             fgp._ensure_ag(len(starts)), fgp._ag_stream)
+    return [(x[r], float(f[r])) for r in range(len(starts))]
+
+
+# -- the polish rounds' host plumbing (DeviceGP and paths.DevicePaths) ------------------------
+class PinnedRound:
+    """The pinned host buffers of one polish round of ``d``-dimensional points -- x, int32
+    ids (acquisition codes or draws), f, g -- which the objective kernels read and write in
+    place: the tensors ``bufs``, their numpy views ``x, ids, f, g`` and addresses ``ptrs``.
+    Grown on demand, never below 16 points."""
+
+    def __init__(self, d):
+        self.d, self.cap = int(d), 0
+
+    def ensure(self, B):
+        if self.cap < B:
+            cap, d = max(16, B), self.d
+            self.bufs = (torch.empty(cap * d, dtype=torch.float64).pin_memory(),
+                         torch.empty(cap, dtype=torch.int32).pin_memory(),
+                         torch.empty(cap, dtype=torch.float64).pin_memory(),
+                         torch.empty(cap * d, dtype=torch.float64).pin_memory())
+            self.x, self.ids, self.f, self.g = (t.numpy() for t in self.bufs)
+            self.ptrs = tuple(t.data_ptr() for t in self.bufs)
+            self.cap = cap
+        return self
+
+    def fg(self, B):
+        """Copies of the round's results: (f (B,), g (B, d))."""
+        return self.f[:B].copy(), self.g[:B * self.d].reshape(B, self.d).copy()
+
+
+def _stage_round(gp, X, ids):
+    """The rows of X (B, d) and their ids into ``gp``'s pinned round: (round, B)."""
+    X = np.asarray(X, dtype=np.float64).reshape(-1, gp.d)
+    B = X.shape[0]
+    r = gp._ensure_ag(B)
+    r.x[:B * gp.d] = X.reshape(-1)
+    r.ids[:B] = ids
+    return r, B
+
+
+def _polish_starts(starts, d):
     starts = np.ascontiguousarray(np.asarray(starts, dtype=np.float64))
+    if starts.ndim != 2 or starts.shape[1] != d:
+        raise ValueError(f"polish starts must be (B, {d}), got {starts.shape}")
+    return starts
+
+
+def _run_polish(symbol, head_args, tail_args, starts, ids, bounds, ftol, maxiter, gtol, maxfun, round, stream):
+    """One of libmpo.so's polish entry points, ``symbol(*head_args, starts, ids, B, bounds,
+    options, *tail_args, round's x / ids / f / g, outputs, stream)``: L-BFGS-B from each row
+    of ``starts`` (B, d) on the objective ``ids[r]`` names.  Returns numpy ``(x (B, d), f (B,),
+    stats (B, 4) = (nit, nfev, status, 0), rounds)``."""
     B, d = starts.shape
-    if d != fgp.d:
-        raise ValueError(f"polish starts must be (B, {fgp.d}), got {starts.shape}")
-    fgp._ensure_ag(B)
-    codes = np.ascontiguousarray(np.asarray(acq_codes, dtype=np.int32))
+    ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
     b = np.ascontiguousarray(np.asarray(bounds, dtype=np.float64).reshape(d, 2))
     opts = _lib.MpoLbfgsbOptions(ftol, gtol, maxiter, maxfun, 10, 20)
     x = np.empty((B, d))
     f = np.empty(B)
     stats = np.empty((B, 4), np.int32)
     rounds = ctypes.c_int32(0)
-    xp, ap, fp, gp = fgp._ag_ptrs
-    rc = lib().mpo_gp_polish_ps_host(ctypes.byref(fgp.model), ctypes.byref(tgp.model), starts.ctypes.data,
-                                     codes.ctypes.data, B, b.ctypes.data, ctypes.byref(opts), float(y_opt), float(xi),
-                                     xp, ap, fp, gp, x.ctypes.data, f.ctypes.data, stats.ctypes.data,
-                                     ctypes.byref(rounds), fgp._ag_stream)
+    rc = getattr(lib(), symbol)(*head_args, starts.ctypes.data, ids.ctypes.data, B, b.ctypes.data, ctypes.byref(opts),
+                                *tail_args, *round.ensure(B).ptrs, x.ctypes.data, f.ctypes.data, stats.ctypes.data,
+                                ctypes.byref(rounds), stream)
     if rc != 0:
-        check(rc, "mpo_gp_polish_ps_host")
-    return [(x[r], float(f[r])) for r in range(B)]
+        check(rc, symbol)
+    return x, f, stats, int(rounds.value)
 
 
 def _normalise(y):

@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr
+from .gp import PinnedRound, _polish_starts, _run_polish
 from .gp_fit import FMIN_FTOL
 
 #: one ``want_samples=True`` evaluation may hold this many bytes of sample rows
@@ -141,16 +142,10 @@ class DevicePaths:
         return f, g
 
     def _ensure_pg(self, B):
-        """Pinned host buffers of one polish round (x, draw ids, f, g) for B runs."""
-        if getattr(self, "_pg_cap", 0) < B:
-            cap = max(16, B)
-            d = self.gp.d
-            self._pg_bufs = (torch.empty(cap * d, dtype=torch.float64).pin_memory(),
-                             torch.empty(cap, dtype=torch.int32).pin_memory(),
-                             torch.empty(cap, dtype=torch.float64).pin_memory(),
-                             torch.empty(cap * d, dtype=torch.float64).pin_memory())
-            self._pg_ptrs = tuple(t.data_ptr() for t in self._pg_bufs)
-            self._pg_cap = cap
+        """The pinned buffers of one polish round (x, draw ids, f, g) for B runs."""
+        if getattr(self, "_pg", None) is None:
+            self._pg = PinnedRound(self.gp.d)
+        return self._pg.ensure(B)
 
     def polish(self, starts, draws, bounds, ftol=FMIN_FTOL, maxiter=20, gtol=1e-5, maxfun=15000):
         """``mpo_gp_paths_polish_host``: L-BFGS-B (libmpo.so's host driver, the settings of
@@ -161,24 +156,12 @@ class DevicePaths:
         L-BFGS-B, a coordinate of ``x`` may pass its bound by one rounding error of the line
         search's ``t + stp d`` (-8.7e-19 was seen at a lower bound 0): clip before use."""
         gp = self.gp
-        starts = np.ascontiguousarray(np.asarray(starts, dtype=np.float64))
-        if starts.ndim != 2 or starts.shape[1] != gp.d:
-            raise ValueError(f"polish starts must be (B, {gp.d}), got {starts.shape}")
-        B, d = starts.shape
+        starts = _polish_starts(starts, gp.d)
+        B = len(starts)
         dr = self._check_draws(draws, B)
         if dr.min() < 0 or dr.max() >= self.s:
             raise ValueError(f"draws outside [0, {self.s})")
-        self._ensure_pg(B)
-        b = np.ascontiguousarray(np.asarray(bounds, dtype=np.float64).reshape(d, 2))
-        opts = _lib.MpoLbfgsbOptions(ftol, gtol, maxiter, maxfun, 10, 20)
-        x = np.empty((B, d))
-        f = np.empty(B)
-        stats = np.empty((B, 4), np.int32)
-        rounds = ctypes.c_int32(0)
-        xp, ip, fp, gp_ = self._pg_ptrs
         with torch.cuda.device(gp.device):
-            check(lib().mpo_gp_paths_polish_host(ctypes.byref(gp.model), ctypes.byref(self.paths), starts.ctypes.data,
-                                                 dr.ctypes.data, B, b.ctypes.data, ctypes.byref(opts), xp, ip, fp, gp_,
-                                                 x.ctypes.data, f.ctypes.data, stats.ctypes.data, ctypes.byref(rounds),
-                                                 _lib.stream_handle(gp.device)), "mpo_gp_paths_polish_host")
-        return x, f, stats, int(rounds.value)
+            return _run_polish("mpo_gp_paths_polish_host", (ctypes.byref(gp.model), ctypes.byref(self.paths)), (),
+                               starts, dr, bounds, ftol, maxiter, gtol, maxfun, self._ensure_pg(B),
+                               _lib.stream_handle(gp.device))

@@ -32,7 +32,7 @@ What decides how a call is launched:
 * ``joint_sample_kernel`` runs ``sample_grid(m, s) = (ceil(mp / 64), ceil(s / 16))`` workgroups,
   one 16-row tile per wave.  ``sample_idle_waves(m)`` waves of the last workgroup have no tile
   and enter the argmin fold with (inf, LLONG_MAX);
-* ``joint_argmin_kernel`` runs ``argmin_blocks(s)`` workgroups of 256 draws.
+* ``argmin_fold_kernel`` (``mpo::argmin_fold``) runs ``argmin_blocks(s)`` workgroups of 256 draws.
 """
 import functools
 import os

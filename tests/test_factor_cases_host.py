@@ -78,8 +78,12 @@ def test_rule_constants_are_the_kernels():
     assert "dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), A, n, lda, info" in src
     assert "for (int i = j + 1 + tid; i < n; i += nt)" in src
     # the polish kernel's LDS: 19 n / 7 n doubles, and the static arrays polish_static_lds sums
-    assert "lds16 = (size_t)19 * model->n * sizeof(double), lds4 = (size_t)7 * model->n * sizeof(double);" in src
-    assert "const bool wide = lds16 + st16 <= kMaxLds;" in src
+    # (the wave-form rule and the kernel's body are gp_grad.h's, shared with gp_ps.hip)
+    grad = open(os.path.join(os.path.dirname(SRC), "gp_grad.h")).read()
+    assert "lds16 = (size_t)19 * n * sizeof(double), lds4 = (size_t)7 * n * sizeof(double);" in grad
+    assert "const bool wide = lds16 + st16 <= kMaxLds;" in grad
+    assert "return mpo::grad_plan(who, model->n, st16, st4, waves, lds);" in src
+    assert "constexpr int kGradThreads = NW * 64, kGroups = kGradThreads / 32;" in grad
     assert "constexpr int kGradThreads = NW * 64, kGroups = kGradThreads / 32;" in src
     assert "__shared__ double xp[32];" in src and "__shared__ double red[kGradThreads];" in src
     assert "__shared__ double ga[kGroups][32], gu[kGroups][32];" in src

@@ -104,8 +104,12 @@ def test_rule_constants_are_the_kernels():
     assert "launch_cov(model, m, mp, w, 1.0, jitter * model->amp, w.A, mp, nullptr, st)" in src
     assert "mpo::blocked_chol(w.A, mp, w.Dinv, info, st)" in src
     assert "dim3(nb, (s + 15) / 16), dim3(256)" in src and "const int i0 = 16 * (4 * blockIdx.x + wave);" in src
-    assert "return v < w || (v == w && i < j);" in src
-    assert "dim3((s + 255) / 256), dim3(256)" in src
+    # the (value, index) order and the argmin fold are shared code: gp_acq_math.h, mpo::argmin_fold
+    csrc = os.path.dirname(SRC)
+    assert "using mpo::lex_less;" in src and "bool lex_less(" not in src
+    assert "return v < w || (v == w && i < j);" in open(os.path.join(csrc, "gp_acq_math.h")).read()
+    assert "mpo::argmin_fold(w.part_val, w.part_idx, s, nb, reinterpret_cast<long long*>(argmin), nullptr, st)" in src
+    assert "dim3((n_draws + 255) / 256), dim3(256)" in open(os.path.join(csrc, "gp_paths.hip")).read()
     hdr = open(os.path.join(ROOT, "include", "mpo.h")).read()
     assert "#define MPO_JOINT_MAX 4096" in hdr and "#define MPO_JOINT_SMAX 1048560" in hdr
     assert J.JOINT_MAX == _lib.MPO_JOINT_MAX == 4096

@@ -126,7 +126,7 @@ def test_rule_constants_are_the_kernels():
 
     dims = re.search(r"#define MPO_SCORE_DIMS\(X\)((?:\s*X\(\d+,\s*\d+\))+)", src)
     assert tuple((int(a), int(b)) for a, b in re.findall(r"X\((\d+),\s*(\d+)\)", dims.group(1))) == C.SCORE_DIMS
-    assert const("kMaxLds") == "160 * 1024" and C.K_MAX_LDS == 160 * 1024
+    assert const("kMaxLds", ihdr) == "160 * 1024" and "using mpo::kMaxLds;" in src and C.K_MAX_LDS == 160 * 1024
     assert int(const("kBM")) == C.K_BM
     assert float(const("kDistNorm")) == C.K_DIST_NORM
     assert int(const("kStreamSlack")) == C.K_STREAM_SLACK
