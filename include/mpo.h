@@ -366,6 +366,59 @@ int mpo_gp_sample(const MpoGpModel* model, const double* cand, int m,
                   int32_t* info, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * PARTIAL DEPENDENCE of a prepared model's posterior mean: the post-analysis of a finished
+ * search.  Replaces the loops of skopt plots.partial_dependence_1D / _2D (plot_objective),
+ * which a user of the reference reaches after Coordinator.run (coordinator.py:102-103) and
+ * which evaluate predict() at every sample with one or two dimensions overwritten by a grid
+ * value.  Reads n, d, dp, amp, y_mean, y_std, xs, ls and alpha only: any prepared, appended
+ * or copied model of n <= 2048 observations is served, whatever its scoring path.
+ *
+ * samples [S][d] (device) are rows of the transformed space.  A task names one or two column
+ * spans [col, col + width) of it (a one-hot Categorical is a span of width > 1; width 0: the
+ * axis is absent -- a 1-D task has no b) and, per span, `count` grid values of `width` doubles
+ * each at grid + grid_off ([count][width], device).  For every cell (ga, gb)
+ *   out[out_off + ga * max(b.count, 1) + gb] =
+ *       y_mean + y_std (1 / S) sum_s sum_i alpha_i amp Matern52(r_si(ga, gb))
+ *   r_si^2 = sum_{k outside the spans} (samples[s][k] / ls_k - xs[i][k])^2
+ *          + sum_{k in a} (grid_a[ga][k] / ls_k - xs[i][k])^2 + sum_{k in b} (grid_b[gb][k] / ls_k - xs[i][k])^2
+ * -- the mean over the samples of the posterior mean at the sample with the spans' columns
+ * overwritten.  The three parts are sums of squares of direct differences (nothing is
+ * subtracted); the first is formed once per tile of samples and observations, the other two
+ * once per axis, and a cell costs S n Matern evaluations.  No atomics; every sum runs in a
+ * fixed order given (S, n), and a task's output bits depend on the model, the samples and
+ * that task alone -- not on T, its position, the other tasks or earlier calls.
+ * ---------------------------------------------------------------------- */
+#define MPO_PD_GMAX 64      /* grid values per axis            */
+#define MPO_PD_SMAX 4096    /* sample rows                     */
+#define MPO_PD_TMAX 1024    /* tasks per call (d = 32: 32 + 496) */
+typedef struct MpoPdAxis {
+    int32_t col, width, count, reserved;   /* width 0: absent */
+    int64_t grid_off;                      /* doubles into grid */
+} MpoPdAxis;
+typedef struct MpoPdTask {
+    MpoPdAxis a, b;
+    int64_t out_off;                       /* doubles into out: [a.count][max(b.count, 1)] */
+} MpoPdTask;
+
+/* Workspace bytes of mpo_gp_partial_dependence: the scaled samples [S][d] and, per task, one
+ * partial sum per cell and split (min(ceil(S / 64), 8) x min(ceil(n / 256), 4) splits:
+ * 4 x 1600 doubles for a 40 x 40 pair at S = 250, n = 200).  0 for anything the call would
+ * refuse. */
+size_t mpo_gp_pd_ws_bytes(const MpoGpModel* model, int S, const MpoPdTask* tasks_host, int T);
+
+/* The T tasks of tasks_host (HOST memory, read during the call: it travels to the kernels by
+ * value, 48 tasks per launch) over one sample set.  MPO_ENOTSUP: n > 2048.  MPO_EINVAL: a null
+ * or unprepared model, a null buffer, S outside [1, MPO_PD_SMAX], T outside [1, MPO_PD_TMAX],
+ * an absent first axis, a span outside [0, d), spans a and b that overlap, a count outside
+ * [1, MPO_PD_GMAX], a negative width or offset, output ranges of two tasks that overlap, a
+ * workspace smaller than mpo_gp_pd_ws_bytes.  All checks run on the host before any launch
+ * (the extents of grid and out are the caller's promise).  Only enqueues work: no allocation,
+ * no host synchronisation, no asynchronous read of host memory; capturable in a graph. */
+int mpo_gp_partial_dependence(const MpoGpModel* model, const double* samples /*[S][d]*/, int S,
+                              const MpoPdTask* tasks_host, int T, const double* grid, double* out,
+                              void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * PATHWISE posterior samples of a prepared model (Matheron's rule; Wilson et al. 2020,
  * "Efficiently sampling functions from Gaussian process posteriors"): a draw is a
  * function that can be evaluated at any point -- a prior draw from F random Fourier

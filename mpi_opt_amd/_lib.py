@@ -19,6 +19,9 @@ MPO_ACQ_LCB = 4
 MPO_TOPK_MAX = 8
 MPO_JOINT_MAX = 4096
 MPO_JOINT_SMAX = 1048560
+MPO_PD_GMAX = 64
+MPO_PD_SMAX = 4096
+MPO_PD_TMAX = 1024
 MPO_PATHS_FMAX = 4096
 MPO_PATHS_SMAX = 1024
 MPO_PATHS_GRAD_BMAX = 8192
@@ -51,6 +54,15 @@ class MpoGpPaths(ctypes.Structure):
         ("Fp", ctypes.c_int32), ("Kp", ctypes.c_int32), ("sp", ctypes.c_int32), ("reserved", ctypes.c_int32),
         ("omega", ctypes.c_void_p), ("phase", ctypes.c_void_p), ("coef", ctypes.c_void_p),
     ]
+
+
+class MpoPdAxis(ctypes.Structure):
+    _fields_ = [("col", ctypes.c_int32), ("width", ctypes.c_int32), ("count", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("grid_off", ctypes.c_int64)]
+
+
+class MpoPdTask(ctypes.Structure):
+    _fields_ = [("a", MpoPdAxis), ("b", MpoPdAxis), ("out_off", ctypes.c_int64)]
 
 
 class MpoDimDesc(ctypes.Structure):
@@ -132,6 +144,8 @@ SIGNATURES = {
     "mpo_gp_joint_ws_bytes": (_SZ, [ctypes.POINTER(MpoGpModel), _I, _I]),
     "mpo_gp_posterior_cov": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _P, _I, _P, _SZ, _P]),
     "mpo_gp_sample": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _I, _D, _P, _P, _P, _P, _SZ, _P]),
+    "mpo_gp_pd_ws_bytes": (_SZ, [ctypes.POINTER(MpoGpModel), _I, _P, _I]),
+    "mpo_gp_partial_dependence": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _I, _P, _P, _P, _SZ, _P]),
     "mpo_gp_paths_ws_bytes": (_SZ, [ctypes.POINTER(MpoGpModel), _I, _I]),
     "mpo_gp_paths_prepare": (_I, [ctypes.POINTER(MpoGpModel), _D, _P, _P, _P, _P, _I, _I, ctypes.POINTER(MpoGpPaths),
                                   _P, _SZ, _P]),

@@ -332,6 +332,39 @@ class DeviceGP:
                   "mpo_gp_sample")
         return {"samples": samples, "argmin": argmin, "info": int(info.item())}
 
+    # -- partial dependence ------------------------------------------------------
+    def partial_dependence(self, samples, tasks):
+        """``mpo_gp_partial_dependence``: the posterior mean averaged over the rows of
+        ``samples`` (S, d) (transformed space, numpy or torch) with one or two column spans
+        overwritten by grid values -- skopt's ``partial_dependence_1D`` / ``_2D`` loops, every
+        task in one call.  A task is ``(col, grid)`` or ``(col_a, grid_a, col_b, grid_b)``;
+        ``grid`` is (count,) for a span of one column or (count, width).  Returns a list of
+        numpy arrays, (count,) or (count_a, count_b) per task."""
+        s = self.as_candidates(samples)
+        S = s.shape[0]
+        table, grid, shapes, total = pd_table(tasks)
+        T = len(shapes)
+        L = lib()
+        need = L.mpo_gp_pd_ws_bytes(ctypes.byref(self.model), S, table, T)
+        if need == 0:   # the call's own host checks name the reason
+            check(L.mpo_gp_partial_dependence(ctypes.byref(self.model), ptr(s), S, table, T, None, None, None, 0,
+                                              None), "mpo_gp_partial_dependence")
+        if getattr(self, "_pd_ws", None) is None or self._pd_ws.numel() < need:
+            self._pd_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        g = torch.from_numpy(grid).to(self.device)
+        out = torch.empty(total, dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            check(L.mpo_gp_partial_dependence(ctypes.byref(self.model), ptr(s), S, table, T, ptr(g), ptr(out),
+                                              ptr(self._pd_ws), self._pd_ws.numel(), _lib.stream_handle(self.device)),
+                  "mpo_gp_partial_dependence")
+        flat = out.cpu().numpy()
+        res, off = [], 0
+        for shp in shapes:
+            k = int(np.prod(shp))
+            res.append(flat[off:off + k].reshape(shp).copy())
+            off += k
+        return res
+
     # -- pathwise samples --------------------------------------------------------
     def paths(self, omega, phase, w, eps, noise=None):
         """``mpo_gp_paths_prepare``: the s sample paths of the random inputs ``omega`` (F, d),
@@ -357,6 +390,37 @@ class DeviceGP:
         mu = out["mu"].cpu().numpy()
         sd = out["sd"].cpu().numpy()
         return (mu, sd) if return_std else mu
+
+
+def pd_table(tasks):
+    """The host task table of ``mpo_gp_partial_dependence`` from ``(col, grid)`` /
+    ``(col_a, grid_a, col_b, grid_b)`` tuples: ``(MpoPdTask array, packed grid float64,
+    output shapes, total output doubles)``; outputs are packed in task order."""
+    tasks = list(tasks)
+    table = (_lib.MpoPdTask * max(len(tasks), 1))()
+    chunks, shapes, goff, ooff = [], [], 0, 0
+
+    def axis(ax, col, grid):
+        nonlocal goff
+        g = np.asarray(grid, dtype=np.float64)
+        g = g.reshape(-1, 1) if g.ndim == 1 else g
+        if g.ndim != 2 or g.size == 0:
+            raise ValueError(f"a grid is (count,) or (count, width), got {np.shape(grid)}")
+        ax.col, ax.width, ax.count, ax.grid_off = int(col), g.shape[1], g.shape[0], goff
+        chunks.append(np.ascontiguousarray(g).reshape(-1))
+        goff += g.size
+        return g.shape[0]
+
+    for t, task in enumerate(tasks):
+        if len(task) not in (2, 4):
+            raise ValueError("a task is (col, grid) or (col_a, grid_a, col_b, grid_b)")
+        na = axis(table[t].a, task[0], task[1])
+        shp = (na,) if len(task) == 2 else (na, axis(table[t].b, task[2], task[3]))
+        table[t].out_off = ooff
+        shapes.append(shp)
+        ooff += int(np.prod(shp))
+    grid = np.concatenate(chunks) if chunks else np.zeros(1)
+    return table, grid, shapes, ooff
 
 
 # -- cost-aware acquisitions (EIps / PIps): two models over the same observations ----------

@@ -131,6 +131,12 @@ def make_parser():
                         "with a cost, and the acquisition is divided by the expected cost.  The cost here is the "
                         "MODELLED training GFLOP per sample of the trial's architecture, not a measured time, and "
                         "it ignores early stopping")
+    p.add_argument("--report", default=None, metavar="PATH",
+                   help="an addition of this build (NOT in the reference, which ends by printing the best "
+                        "observed point): after the last tell, rank 0 writes the objective report to PATH as JSON "
+                        "-- the partial dependence of every dimension and pair, each dimension's importance and "
+                        "the surrogate's expected minimum (mpi_opt_amd.analysis.objective_report; its samples come "
+                        "from its own seed, never from the optimizer's stream)")
     return p
 
 
@@ -343,6 +349,12 @@ def run_search(args, x=None, y=None, log=print, progress=None, on_population=Non
         "best_fom": state.best_fom, "best_params": state.best_params,
         "gp": dict(_opt_mod.STATS),     # refits (tell + every cl_min lie), their n, refit / proposal seconds
     }
+    if getattr(args, "report", None):
+        from .analysis import objective_report, write_report
+
+        write_report(objective_report(sched.optimizer), args.report)
+        report["report"] = args.report
+        log(f"objective report written to {args.report}")
     log(f"search done: {report['trials_trained']} trials trained ({report['trials_told']} told) in "
         f"{wall:.1f} s; optimizer {report['optimizer_s']:.2f} s, training {report['train_s']:.1f} s; "
         f"best {state.best_fom} at {state.best_params}")
