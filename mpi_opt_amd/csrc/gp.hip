@@ -105,6 +105,19 @@ __device__ __forceinline__ double sqrt_pos(double r2) {
 // first term of every pairwise squared-distance sum (see sqrt_pos)
 constexpr double kR2Floor = 1e-300;
 
+// max(acc[r], kR2Floor) of an MFMA distance tile, one v_max_f64 per register with the
+// floor in an SGPR pair.  fmax() compiles to two: it first canonicalises its argument
+// (v_max x, x, x), which only matters for a signalling NaN, and an MFMA result never
+// is one.  The bits are fmax's.  The compiler does not count inline asm among the
+// VALU readers of an MFMA result, so the block carries the wait states itself: 19
+// between a v_mfma_f64_16x16x4_f64 and the first VALU read of its result, what the
+// compiler puts in front of fmax().
+__device__ __forceinline__ void clamp_r2x4(f64x4 acc, double (&r2)[4]) {
+    asm("s_nop 15\n\ts_nop 2" : "+v"(acc));   // tied to the whole result tuple: it stays behind the MFMAs
+#pragma unroll
+    for (int r = 0; r < 4; ++r) asm("v_max_f64 %0, %1, %2" : "=v"(r2[r]) : "v"(acc[r]), "s"(kR2Floor));
+}
+
 // The scoring kernel's Matern WITHOUT the ConstantKernel amplitude:
 // (1 + k + k^2/3) exp(-k), k = sqrt(5 r2), k^2/3 = r2 * 5/3.  The kernel folds amp
 // into mu (amp * K'.alpha) and into q (amp^2 ||L^-1 K'||^2): one multiply fewer per
@@ -116,13 +129,33 @@ __device__ __forceinline__ double matern52_unit(double r2) {
 }
 
 // Sum over the 16 lanes of a row group: with the f64 MFMA C/D map (col = lane & 15,
-// row = (lane >> 4) + 4 r) the sum of a C register over the tile's 16 columns.
-__device__ __forceinline__ double colsum16(double v) {
-    v += __shfl_xor(v, 1);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 4);
-    v += __shfl_xor(v, 8);
-    return v;
+// row = (lane >> 4) + 4 r) the sum of a C register over the tile's 16 columns, for
+// four registers at once (colsum16x4 below).
+// The four steps are DPP moves of the two 32-bit halves (no LDS round trip) plus one
+// v_add_f64 each: quad_perm [1,0,3,2] and [2,3,0,1] are lane ^ 1 and lane ^ 2 exactly.
+// After them every quad is uniform, so row_half_mirror's lane 7 - i holds what lane
+// i ^ 4 holds; after that step every group of 8 is uniform, so row_mirror's lane
+// 15 - i holds what lane i ^ 8 holds.  fp64 addition is commutative: every lane adds
+// the same two values as the xor butterfly (v += shfl_xor(v, 1 / 2 / 4 / 8)) did, and
+// every bit of the sum is the butterfly's.  A DPP move reads nothing from a lane that
+// EXEC masks off: the callers are wave-uniform code of kernels launched with whole
+// 64-lane waves (both scoring kernels' mu / q folds).
+template <int CTRL>
+__device__ __forceinline__ double dpp_move_f64(double v) {
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+// four registers folded step by step, so that the four chains interleave
+__device__ __forceinline__ void colsum16x4(double (&v)[4]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] += dpp_move_f64<0xB1>(v[r]);    // quad_perm:[1,0,3,2]
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] += dpp_move_f64<0x4E>(v[r]);    // quad_perm:[2,3,0,1]
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] += dpp_move_f64<0x141>(v[r]);   // row_half_mirror
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] += dpp_move_f64<0x140>(v[r]);   // row_mirror
 }
 
 // Rows [n, rows) of xs are zero padding (alpha and the L^-1 fragments are zero
@@ -635,26 +668,64 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
                     af[s] = kk == D ? cc : kk == D + 1 ? 1.0 : v;
                 }
                 const int T16 = np16 >> 4;
-                const double* xbl = a.xb + (size_t)(lane & 15) * DP + kr;
-                double bq[DP / 4];
                 double mu4[4] = {0.0, 0.0, 0.0, 0.0};
-                for (int t = vs; t < T16; t += 4) {
-#pragma unroll
-                    for (int s = 0; s < DP / 4; ++s) bq[s] = xbl[(size_t)t * 16 * DP + 4 * s];
-                    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                    for (int s = 0; s < DP / 4; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(af[s], bq[s], acc, 0, 0, 0);
-                    const int i = t * 16 + (lane & 15);
-                    const double al = a.alpha[i];
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const double kv = matern52_unit(fmax(acc[r], kR2Floor));
-                        kc[(size_t)(i >> 2) * 64 + kr + 4 * r + (i & 3) * 16] = kv;
-                        mu4[r] = fma(kv, al, mu4[r]);
-                    }
+                // Block t's xb fragments and alpha arrive through asm loads issued one
+                // block ahead, right behind block t - 4's MFMAs (bq is dead from there),
+                // so their latency runs under that block's Matern instead of in front
+                // of this block's MFMAs.  As for phase 2's ring, the compiler neither
+                // sees nor waits for these loads: every use of bq / al is tied to the
+                // explicit wait at the loop's top, alpha is copied out of its load
+                // register by an asm move directly behind that wait (a plain copy was
+                // sunk below the next load's issue), and the loop drains before the mu
+                // fold, so a tile on the direct form never meets a load in flight.  The
+                // last block's prefetch re-reads that block (a scalar select): nothing
+                // past the wave's own blocks is touched, and a wave whose share is
+                // empty (vs >= T16) neither loads nor waits.
+                const int xoff = ((lane & 15) * DP + kr) * 8, aoff = (lane & 15) * 8;   // lane byte offsets
+                double bq[DP / 4], al;
+#define MPO_P1_LD(S)                                                                               \
+                if constexpr (S < DP / 4)                                                          \
+                    asm volatile("global_load_dwordx2 %0, %1, %2 offset:%3"                        \
+                                 : "=v"(bq[S]) : "v"(xoff), "s"(xp), "n"(32 * S) : "memory");
+#define MPO_P1_LOAD(TT)                                                                            \
+                {                                                                                  \
+                    const double* xp = a.xb + (size_t)(TT) * 16 * DP;                              \
+                    const double* alp = a.alpha + (size_t)(TT) * 16;                               \
+                    MPO_P1_LD(0) MPO_P1_LD(1) MPO_P1_LD(2) MPO_P1_LD(3)                            \
+                    MPO_P1_LD(4) MPO_P1_LD(5) MPO_P1_LD(6) MPO_P1_LD(7)                            \
+                    asm volatile("global_load_dwordx2 %0, %1, %2" : "=v"(al) : "v"(aoff), "s"(alp) : "memory"); \
                 }
+                static_assert(DP / 4 <= 8, "MPO_P1_LOAD issues at most 8 fragment loads");
+                if (vs < T16) {
+                    MPO_P1_LOAD(vs)
+                    for (int t = vs; t < T16; t += 4) {
+                        asm volatile("s_waitcnt vmcnt(0)" : "+v"(al));
 #pragma unroll
-                for (int r = 0; r < 4; ++r) mu4[r] = colsum16(mu4[r]);
+                        for (int s = 0; s < DP / 4; ++s) asm volatile("" : "+v"(bq[s]));
+                        double alc;
+                        asm volatile("v_mov_b64 %0, %1" : "=v"(alc) : "v"(al));
+                        f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                        for (int s = 0; s < DP / 4; ++s) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(af[s], bq[s], acc, 0, 0, 0);
+                        const int tn = t + 4 < T16 ? t + 4 : t;
+                        MPO_P1_LOAD(tn)
+                        const int i = t * 16 + (lane & 15);
+                        double r2[4];
+                        clamp_r2x4(acc, r2);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const double kv = matern52_unit(r2[r]);
+                            kc[(size_t)(i >> 2) * 64 + kr + 4 * r + (i & 3) * 16] = kv;
+                            mu4[r] = fma(kv, alc, mu4[r]);
+                        }
+                    }
+                    asm volatile("s_waitcnt vmcnt(0)" : "+v"(al));
+#pragma unroll
+                    for (int s = 0; s < DP / 4; ++s) asm volatile("" : "+v"(bq[s]));
+                }
+#undef MPO_P1_LOAD
+#undef MPO_P1_LD
+                colsum16x4(mu4);
                 // the share's row of this tile's mu partials
                 if ((lane & 15) == 0) {
 #pragma unroll
@@ -705,6 +776,12 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
         double sq[4] = {0.0, 0.0, 0.0, 0.0};
         f64x4 acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
         int t = 0, kg = 0, tlen = __builtin_amdgcn_readfirstlane(mw[3] + 1);
+        // the next column tile's length, read one tile ahead: the LDS read at a
+        // column tile's end is for the tile after the next, so nothing at the MFMA
+        // drain waits for it.  (The record's jt list is zero-filled to T + 1 entries;
+        // the read one past that, taken only by the wave that owns every tile of a
+        // T = 1 model, stays inside mls and its value is never used.)
+        int tnext = __builtin_amdgcn_readfirstlane(mw[4] + 1);
         // one group: 4 MFMAs on two accumulation chains, then the ring slot is
         // refilled with the group two ahead; at a column tile's last group
         // ||V_row||^2 takes the tile's columns
@@ -723,7 +800,8 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
                 acc0 = f64x4{0.0, 0.0, 0.0, 0.0};                                                  \
                 acc1 = f64x4{0.0, 0.0, 0.0, 0.0};                                                  \
                 kg = 0;                                                                            \
-                tlen = __builtin_amdgcn_readfirstlane(mw[3 + (++t)] + 1);                          \
+                tlen = tnext;                                                                      \
+                tnext = __builtin_amdgcn_readfirstlane(mw[4 + (++t)] + 1);                         \
             }                                                                                      \
         }
         for (int g = 0; g < G; g += 2) {
@@ -734,11 +812,12 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(b0[0]), "+v"(b0[1]), "+v"(b0[2]), "+v"(b0[3]), "+v"(b1[0]),
                      "+v"(b1[1]), "+v"(b1[2]), "+v"(b1[3]));
 #undef MPO_EI_GROUP
-        // f64 C/D map: col = lane & 15, row = (lane >> 4) + 4 r.  Sum the columns.
+        // f64 C/D map: col = lane & 15, row = (lane >> 4) + 4 r.  Sum the columns:
+        // all four folds first, then the stores
+        colsum16x4(sq);
+        if ((lane & 15) == 0) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const double v = colsum16(sq[r]);
-            if ((lane & 15) == 0) redq[wave * BM + (lane >> 4) + 4 * r] = v;
+            for (int r = 0; r < 4; ++r) redq[wave * BM + (lane >> 4) + 4 * r] = sq[r];
         }
     }
     // Barrier D: every wave is done with K* (the next phase 1 rewrites kc), and the
@@ -909,10 +988,10 @@ __global__ __launch_bounds__(256) void gp_score_streamed_kernel(ScoreArgs a) {
         // ---- (mu_n, q) row: mu over the 16 slots, q over the 4 waves' column sums
         // (f64 C/D map: col = lane & 15, row = (lane >> 4) + 4 r)
         red[slot * BM + row] = mu_acc;
+        colsum16x4(sq);
+        if ((lane & 15) == 0) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const double v = colsum16(sq[r]);
-            if ((lane & 15) == 0) red[(S + wave) * BM + (lane >> 4) + 4 * r] = v;
+            for (int r = 0; r < 4; ++r) red[(S + wave) * BM + (lane >> 4) + 4 * r] = sq[r];
         }
         __syncthreads();
         if (wave == 0 && lane < BM && m0 + lane < a.m) {
