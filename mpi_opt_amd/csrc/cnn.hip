@@ -1465,8 +1465,22 @@ struct Seg {
 inline int item_sub(const WgItem& x) { return x.R; }
 template <class T>
 inline int item_sub(const T&) { return 0; }
-struct Bucketed {
-    std::vector<Seg> segs;
+
+// One work list of the plan, with everything that belongs to it.  `full` holds every
+// member's items in creation order, as build_plan generated them; `items` the ACTIVE
+// members' (mpo_pop_set_active), which is what the device table at `off` holds:
+// apply_mask filters `full` by item.member and buckets / deals the result as for a
+// fresh plan.  A bucketed list (one launch per segment; `name` is its profile label)
+// also keeps what the bucketing needs and yields: per-member LDS bytes and the segments.
+template <class T>
+struct WorkList {
+    const char* name;
+    bool bucketed = false;
+    std::vector<T> full, items;
+    size_t off = 0;            // byte offset of the device table
+    std::vector<size_t> lds;   // bucketed: [member] dynamic LDS bytes of this op
+    std::vector<Seg> segs;     // bucketed: launch segments of `items`
+    size_t size() const { return items.size(); }
 };
 
 // Per-phase device timing for diagnostics (env MPO_POP_PROFILE=1 at plan
@@ -1478,8 +1492,9 @@ struct PhaseTimer {
     std::vector<std::string> names;
     int used = 0;
     std::vector<std::pair<std::string, double>> acc;
+    bool live() const { return on && !mpo::g_tally; }   // a tally walk records nothing
     void mark(const std::string& name, hipStream_t s) {
-        if (!on) return;
+        if (!live()) return;
         if (used == (int)ev.size()) {
             hipEvent_t e;
             if (hipEventCreate(&e) != hipSuccess) { on = false; return; }
@@ -1535,57 +1550,95 @@ struct Plan {
     int debug = 0;
     std::vector<Member> mem;
     long long n_params = 0, act_floats = 0;
-    std::vector<ConvItem> conv1, conv2, dgrad, dgf;
-    Bucketed bc1, bc2, bdg, bdf;
-    std::vector<WgItem> wg1, wg2;
-    Bucketed bw1, bw2;
-    std::vector<GemmItem> d1f, d2f, d2w, d2d, d1w, d1d;
-    std::vector<MItem> per_member, per_sample, colsum, wred, adam;
-    // Every member's work in creation order, as build_plan generated it, with what the
-    // bucketing needs (per-member LDS bytes per op, the occmerge / xcd knobs).  The
-    // lists above are the ACTIVE members' (mpo_pop_set_active): apply_mask filters
-    // these by item.member and buckets / deals the result as for a fresh plan.
-    struct FullLists {
-        std::vector<ConvItem> conv1, conv2, dgrad, dgf;
-        std::vector<WgItem> wg1, wg2;
-        std::vector<GemmItem> d1f, d2f, d2w, d2d, d1w, d1d;
-        std::vector<MItem> per_member, per_sample, colsum, adam;
-    } full;
-    std::vector<size_t> L1, L2, LD, LDF, LW1, LW2;
-    int occmerge = 2, xcd = 4;
+    // The work lists, each declared once; for_each_list below visits them all.  wred is
+    // derived: apply_mask rebuilds it from per_member.
+    WorkList<ConvItem> conv1{"conv1_fwd", true}, conv2{"conv2_fwd", true}, dgrad{"conv2_dgrad", true},
+        dgf{"conv2_dgrad_fwd", true};
+    WorkList<WgItem> wg1{"conv1_wgrad", true}, wg2{"conv2_wgrad", true};
+    WorkList<GemmItem> d1f{"d1f"}, d2f{"d2f"}, d2w{"d2w"}, d2d{"d2d"}, d1w{"d1w"}, d1d{"d1d"};
+    WorkList<MItem> per_member{"per_member"}, per_sample{"per_sample"}, colsum{"colsum"}, wred{"wred"}, adam{"adam"};
     std::vector<uint8_t> active;   // [n] 0 / 1
     int na = 0;                    // active members: per_member.size()
     int adam_chunk = 8192;
     int wred_per_block = 4096, wred_blocks = 1;
-    // device tables
+    // device tables: the Member table at off_mem, then every list's at its `off`
     char* table_base = nullptr;
-    size_t table_bytes = 0;
+    size_t table_bytes = 0, off_mem = 0;
     std::vector<char> host_tables;
-    size_t off_mem, off_conv1, off_conv2, off_dgrad, off_dgf, off_wg1, off_wg2, off_d1f, off_d2f, off_d2w, off_d2d,
-        off_d1w, off_d1d, off_pm, off_ps, off_cs, off_wr, off_adam;
     float *params = nullptr, *grads = nullptr, *m = nullptr, *v = nullptr, *act = nullptr;
     bool bound = false;
     size_t lds_conv_max = 0, lds_wg_max = 0;
+    // MPO_POP_PLAN knobs, read once per plan by read_knobs
     int conv_mt = 4;        // forward conv m-tiles per wave at most: items of up to 256 pixels (MPO_POP_PLAN conv_mt=2: 128)
+    int conv_kb1 = 30, conv_kb2 = 100;   // forward conv LDS budgets per workgroup, KiB (choose_rows)
     int dg_tiles = 12;      // 4x4 tiles per conv2 input-gradient work item at most (MPO_POP_PLAN dg_tiles)
+    int dg_kb = 78;         // conv2 input-gradient LDS budget per workgroup, KiB
     int dgfset = 0;         // ... and members whose bit k is set (MPO_POP_PLAN dgfset, a mask over k)
     int dgfwd = 4;          // r06: members with k <= dgfwd take the zero-bordered forward conv for their input gradient (MPO_POP_PLAN dgfwd)
+    int dgf_kb1 = 80, dgf_kb2 = 100;     // ... and that conv's LDS budgets, KiB (dgf_kb2 defaults to conv_kb2)
     int wgrpb = 2;          // conv2 weight gradient output rows per barrier (MPO_POP_PLAN wgrpb = 1 | 2)
     int wgpair = 1;         // r06: with wgrpb 2, a row pair of Ho = 2 (mod 4) pixels as one K run (MPO_POP_PLAN wgpair)
-    // Second stream for independent launches (MPO_POP_PLAN streams=1 keeps one): the
-    // forward conv2 buckets alternate between the two, and the conv2 weight gradient
-    // runs beside the input gradient + conv1 weight gradient, so one launch's tail
-    // overlaps the other's work.  No two concurrent kernels write the same buffer.
-    mpo::SideStream side;
-    mpo::SideStream side4;   // r06: a third stream for the input-gradient buckets (plan knob dgs = 3, the default; 2: two)
-    mpo::SideStream side3;   // r06: conv2 weight-gradient buckets alternate over side and side3 (plan knob wgs = 2, the default; 1: one stream)
-    mpo::SideStream side2;   // a third stream: the input-gradient buckets alternate over s and it
+    int occmerge = 2, occfill = 4, xcd = 4;   // bucket_segs, xcd_deal
+    // Side streams for independent launches (MPO_POP_PLAN streams=1 keeps one stream), each
+    // with its slot in the process-wide pool.  No two concurrent kernels write the same
+    // buffer, and one launch's tail overlaps the other's work.
+    // conv2 forward / weight gradient: the forward conv2 buckets alternate over s and it; in the
+    // backward the dense and conv2 weight gradients run on it beside the input gradients on s
+    mpo::SideStream side_wg{0};
+    // r06: the conv2 weight-gradient buckets alternate over side_wg and it (plan knob wgs = 2, the default; 1: one stream)
+    mpo::SideStream side_wg_alt{2};
+    // the conv2 input-gradient buckets alternate over s and it (streams = 3, the default)
+    mpo::SideStream side_dg{1};
+    // r06: ... and over it as a third (plan knob dgs = 3, the default; 2: two)
+    mpo::SideStream side_dg_alt{3};
 };
 
-size_t conv_lds_bytes(int rows, int Wp, int Cin, int Ho, int K, int nt) {
-    (void)nt;
-    const int Fp = fwd_fp(Cin);
-    (void)Fp;
+// Every work list, in the order of the device tables.
+template <class PlanT, class Fn>
+void for_each_list(PlanT& P, Fn&& fn) {
+    fn(P.conv1); fn(P.conv2); fn(P.dgrad); fn(P.dgf); fn(P.wg1); fn(P.wg2);
+    fn(P.d1f); fn(P.d2f); fn(P.d2w); fn(P.d2d); fn(P.d1w); fn(P.d1d);
+    fn(P.per_member); fn(P.per_sample); fn(P.colsum); fn(P.wred); fn(P.adam);
+}
+
+// Every once-per-plan MPO_POP_PLAN knob (see plan_knob).  The samples-per-slab knobs wg_spg*
+// stay where build_plan applies them, member by member.
+void read_knobs(Plan& P) {
+    P.conv_mt = plan_knob("conv_mt", 4) == 2 ? 2 : 4;
+    // r06, after dgfwd + wgpair (profiles/r06/mnist/av_*, aw_*): a 30 KiB first budget, 37.41 / 37.28 ->
+    // 37.13 / 37.08 ms per 320-member step, 3.95 -> 3.86 ms at 40, 1.633 -> 1.642 at 20 (24 and 36 alike)
+    P.conv_kb1 = plan_knob("conv_kb1", 30);
+    P.conv_kb2 = plan_knob("conv_kb2", 100);
+    // r03: at most 12 tiles (3 per wave): conv2 dgrad 15.40 -> 15.15 ms per 320-member batch
+    // (profiles/r03/train_sweep_dgtiles_ap.log; 16 was r01-r02's, 8 measured 16.96)
+    P.dg_tiles = std::max(1, std::min(16, plan_knob("dg_tiles", 12)));
+    P.dg_kb = plan_knob("dg_kb", 78);
+    P.dgfwd = plan_knob("dgfwd", 4);
+    P.dgfset = plan_knob("dgfset", 0);
+    P.dgf_kb1 = plan_knob("dgf_kb1", 80);
+    P.dgf_kb2 = plan_knob("dgf_kb2", P.conv_kb2);
+    P.wgrpb = plan_knob("wgrpb", 2) == 1 ? 1 : 2;
+    // r06, MI355X (profiles/r06/mnist/as_*.log): 37.70 -> 37.29 ms per 320-member step,
+    // 1.64 -> 1.63 ms at 20; losses bit-identical (a padding pixel's MFMA product is an exact zero)
+    P.wgpair = plan_knob("wgpair", 1);
+    // Small populations (a distributed shard, configs[0]) launch too few workgroups per occupancy class
+    // to fill the chip.  Merging every class of an (NT, sub) bucket (mode 1) measured on MI355X
+    // (profiles/r05/occmerge_o.log): 20 members 3.82 -> 3.52 ms, 40: 5.93 -> 5.70, 80: 10.94 -> 10.96,
+    // 160: 19.81 -> 20.30, 320: 36.92 -> 39.06 ms per train step.  Merging only adjacent classes
+    // short of one full wave (mode 2, the default): 20: 3.53, 40: 5.56-5.59, 80: 10.63-10.67,
+    // 320: 36.81-36.95 (separate classes 36.87) -- profiles/r05/occmerge2_*.log.  The segmenting
+    // changes no arithmetic.
+    P.occmerge = plan_knob("occmerge", 2);
+    P.occfill = std::max(1, plan_knob("occfill", 4));   // quarter waves
+    P.xcd = plan_knob("xcd", 4);
+    const int streams = plan_knob("streams", 3);
+    P.side_wg.enabled = streams >= 2;
+    P.side_dg.enabled = streams >= 3;
+    P.side_wg_alt.enabled = P.side_wg.enabled && plan_knob("wgs", 2) >= 2;
+    P.side_dg_alt.enabled = P.side_dg.enabled && plan_knob("dgs", 3) >= 3;
+}
+
+size_t conv_lds_bytes(int rows, int Wp, int Cin, int Ho, int K) {
     return (size_t)(align4(rows * fwd_rs(Wp, Cin, Ho)) + ((K + 15) & ~15) + kKoffSlack) * sizeof(float);
 }
 
@@ -1594,7 +1647,7 @@ size_t dgrad_lds_bytes(int R, int k, int F, int H2) {
     return (size_t)(align4(rows * dgrad_rs(H2, F)) + 64) * sizeof(float);
 }
 
-size_t wg_lds_bytes(int k, int Hin, int Cin, int Ho, int F, int rpb = 1) {
+size_t wg_lds_bytes(int k, int Hin, int Cin, int Ho, int F, int rpb) {
     const int ring = round64((k + 1 + rpb) * round64(Hin * Cin) + 8 * Cin + 64);
     const int dS = round64((4 * ((Ho + 3) >> 2) + 4) * F + 64);
     return (size_t)(ring + (2 + rpb) * dS + kWgWaves * 64 + 4) * sizeof(float);
@@ -1620,16 +1673,18 @@ int lds_class(size_t lds) { return (int)std::min<size_t>(8, ((size_t)160 << 10) 
 // mode 0: one segment per (NT, sub, occupancy class); 1: one per (NT, sub) at the
 // largest member's LDS; 2: adjacent occupancy classes of one (NT, sub) merge while
 // either of them is short of one full wave of workgroups at its own occupancy
+// (fill4 quarter waves: the occfill knob)
 template <class T>
-void bucket_segs(std::vector<T>& items, Bucketed& bk, const std::vector<Member>& mem, const std::vector<size_t>& lds,
-                 int mode = 0) {
+void bucket_segs(WorkList<T>& L, const std::vector<Member>& mem, int mode, long long fill4) {
+    std::vector<T>& items = L.items;
+    const std::vector<size_t>& lds = L.lds;
     const bool by_occupancy = mode != 1;
     // by_occupancy = false: one segment per (NT, sub) at the largest member's LDS (fewer, fuller launches)
     auto key = [&](const T& x) {
         return (mem[x.member].nt * 8 + item_sub(x)) * 16 + (by_occupancy ? 8 - lds_class(lds[x.member]) : 0);
     };
     std::stable_sort(items.begin(), items.end(), [&](const T& x, const T& y) { return key(x) < key(y); });
-    bk.segs.clear();
+    L.segs.clear();
     for (int i = 0; i < (int)items.size();) {
         const int kk = key(items[i]);
         Seg sg{mem[items[i].member].nt, i, i, 0, item_sub(items[i])};
@@ -1638,9 +1693,8 @@ void bucket_segs(std::vector<T>& items, Bucketed& bk, const std::vector<Member>&
             ++i;
         }
         sg.end = i;
-        if (mode == 2 && !bk.segs.empty()) {
-            Seg& pv = bk.segs.back();
-            static const long long fill4 = std::max(1, plan_knob("occfill", 4));   // quarter waves
+        if (mode == 2 && !L.segs.empty()) {
+            Seg& pv = L.segs.back();
             const long long full_pv = 64LL * fill4 * lds_class(pv.lds), full_sg = 64LL * fill4 * lds_class(sg.lds);
             if (pv.nt == sg.nt && pv.sub == sg.sub &&
                 (pv.end - pv.begin < full_pv || sg.end - sg.begin < full_sg)) {
@@ -1649,7 +1703,7 @@ void bucket_segs(std::vector<T>& items, Bucketed& bk, const std::vector<Member>&
                 continue;
             }
         }
-        bk.segs.push_back(sg);
+        L.segs.push_back(sg);
     }
 }
 
@@ -1670,10 +1724,11 @@ void bucket_segs(std::vector<T>& items, Bucketed& bk, const std::vector<Member>&
 // the kernels are issue-bound, not HBM-bound); c = 2 / 8 / 16 / 32: 37.2-37.4 ms.
 // MPO_POP_PLAN xcd=0 restores the plain order.
 template <class T>
-void xcd_deal(std::vector<T>& items, const Bucketed& bk, int c) {
+void xcd_deal(WorkList<T>& L, int c) {
     if (c <= 1) return;
+    std::vector<T>& items = L.items;
     std::vector<T> out;
-    for (const Seg& sg : bk.segs) {
+    for (const Seg& sg : L.segs) {
         const int n = sg.end - sg.begin;
         if (n <= 8) continue;
         std::vector<std::vector<int>> q(8);
@@ -1702,13 +1757,6 @@ int wg_mt(int Kw, int mg) {
     return std::max(1, std::min(kWgMaxMT, (tiles + kWgWaves - 1) / kWgWaves));
 }
 
-template <class T>
-void keep_active(const std::vector<T>& full, const std::vector<uint8_t>& active, std::vector<T>& out) {
-    out.clear();
-    for (const T& x : full)
-        if (active[x.member]) out.push_back(x);
-}
-
 // The active members' work lists from the full ones (P.active), bucketed and dealt
 // exactly as a plan created from the active specs alone would have them: the
 // filtered lists keep the creation order, and the segmenting only looks at each
@@ -1716,47 +1764,26 @@ void keep_active(const std::vector<T>& full, const std::vector<uint8_t>& active,
 // the arenas do not move).  No arithmetic depends on the segmenting or on the
 // item order, so an active member's bits do not change.
 void apply_mask(Plan& P) {
-    const Plan::FullLists& F = P.full;
-    keep_active(F.conv1, P.active, P.conv1);
-    keep_active(F.conv2, P.active, P.conv2);
-    keep_active(F.dgrad, P.active, P.dgrad);
-    keep_active(F.dgf, P.active, P.dgf);
-    keep_active(F.wg1, P.active, P.wg1);
-    keep_active(F.wg2, P.active, P.wg2);
-    keep_active(F.d1f, P.active, P.d1f);
-    keep_active(F.d2f, P.active, P.d2f);
-    keep_active(F.d2w, P.active, P.d2w);
-    keep_active(F.d2d, P.active, P.d2d);
-    keep_active(F.d1w, P.active, P.d1w);
-    keep_active(F.d1d, P.active, P.d1d);
-    keep_active(F.per_member, P.active, P.per_member);
-    keep_active(F.per_sample, P.active, P.per_sample);
-    keep_active(F.colsum, P.active, P.colsum);
-    keep_active(F.adam, P.active, P.adam);
+    for_each_list(P, [&](auto& L) {   // wred: its `full` is empty, it is rebuilt below
+        L.items.clear();
+        for (const auto& x : L.full)
+            if (P.active[x.member]) L.items.push_back(x);
+        if (L.bucketed) {
+            bucket_segs(L, P.mem, P.occmerge, P.occfill);
+            xcd_deal(L, P.xcd);
+        }
+    });
     P.na = (int)P.per_member.size();
     // slab reductions, addressed by halves: conv2 slabs are items [0, na) (reduced on
     // the side stream), conv1 slabs items [na, 2 na)
-    P.wred.clear();
-    for (const MItem& it : P.per_member) P.wred.push_back({it.member, 1});
-    for (const MItem& it : P.per_member) P.wred.push_back({it.member, 0});
+    for (const MItem& it : P.per_member.items) P.wred.items.push_back({it.member, 1});
+    for (const MItem& it : P.per_member.items) P.wred.items.push_back({it.member, 0});
     long long wmax = 1;
-    for (const MItem& it : P.per_member) {
+    for (const MItem& it : P.per_member.items) {
         const Member& m = P.mem[it.member];
         wmax = std::max(wmax, (long long)m.k * m.k * m.F * m.F + m.F);
     }
     P.wred_blocks = (int)((wmax + P.wred_per_block - 1) / P.wred_per_block);
-    bucket_segs(P.conv1, P.bc1, P.mem, P.L1, P.occmerge);
-    bucket_segs(P.conv2, P.bc2, P.mem, P.L2, P.occmerge);
-    bucket_segs(P.dgrad, P.bdg, P.mem, P.LD, P.occmerge);
-    bucket_segs(P.dgf, P.bdf, P.mem, P.LDF, P.occmerge);
-    bucket_segs(P.wg1, P.bw1, P.mem, P.LW1, P.occmerge);
-    bucket_segs(P.wg2, P.bw2, P.mem, P.LW2, P.occmerge);
-    xcd_deal(P.conv1, P.bc1, P.xcd);
-    xcd_deal(P.conv2, P.bc2, P.xcd);
-    xcd_deal(P.dgrad, P.bdg, P.xcd);
-    xcd_deal(P.dgf, P.bdf, P.xcd);
-    xcd_deal(P.wg1, P.bw1, P.xcd);
-    xcd_deal(P.wg2, P.bw2, P.xcd);
 }
 
 // Serialise the tables for one device upload.  layout = true (mpo_pop_create, every
@@ -1764,62 +1791,22 @@ void apply_mask(Plan& P) {
 // rewrite the same region in place: an active list is never longer than the full one.
 void write_tables(Plan& P, bool layout) {
     size_t off = 0;
-    auto put = [&](size_t& slot, const void* src, size_t bytes) {
+    auto put = [&](size_t& slot, const auto& v) {
+        const size_t bytes = v.size() * sizeof(v[0]);
         if (layout) {
             off = mpo::align_up(off, 256);
             slot = off;
             off += bytes;
             P.host_tables.resize(off);
         }
-        if (bytes) std::copy_n(static_cast<const char*>(src), bytes, P.host_tables.data() + slot);
+        if (bytes) std::copy_n(reinterpret_cast<const char*>(v.data()), bytes, P.host_tables.data() + slot);
     };
-    put(P.off_mem, P.mem.data(), P.mem.size() * sizeof(Member));
-    put(P.off_conv1, P.conv1.data(), P.conv1.size() * sizeof(ConvItem));
-    put(P.off_conv2, P.conv2.data(), P.conv2.size() * sizeof(ConvItem));
-    put(P.off_dgrad, P.dgrad.data(), P.dgrad.size() * sizeof(ConvItem));
-    put(P.off_dgf, P.dgf.data(), P.dgf.size() * sizeof(ConvItem));
-    put(P.off_wg1, P.wg1.data(), P.wg1.size() * sizeof(WgItem));
-    put(P.off_wg2, P.wg2.data(), P.wg2.size() * sizeof(WgItem));
-    put(P.off_d1f, P.d1f.data(), P.d1f.size() * sizeof(GemmItem));
-    put(P.off_d2f, P.d2f.data(), P.d2f.size() * sizeof(GemmItem));
-    put(P.off_d2w, P.d2w.data(), P.d2w.size() * sizeof(GemmItem));
-    put(P.off_d2d, P.d2d.data(), P.d2d.size() * sizeof(GemmItem));
-    put(P.off_d1w, P.d1w.data(), P.d1w.size() * sizeof(GemmItem));
-    put(P.off_d1d, P.d1d.data(), P.d1d.size() * sizeof(GemmItem));
-    put(P.off_pm, P.per_member.data(), P.per_member.size() * sizeof(MItem));
-    put(P.off_ps, P.per_sample.data(), P.per_sample.size() * sizeof(MItem));
-    put(P.off_cs, P.colsum.data(), P.colsum.size() * sizeof(MItem));
-    put(P.off_wr, P.wred.data(), P.wred.size() * sizeof(MItem));
-    put(P.off_adam, P.adam.data(), P.adam.size() * sizeof(MItem));
+    put(P.off_mem, P.mem);
+    for_each_list(P, [&](auto& L) { put(L.off, L.items); });
     if (layout) {
         P.table_bytes = mpo::align_up(off, 256);
         P.host_tables.resize(P.table_bytes);
     }
-}
-
-// Workgroups and launches of one train step under the current mask, as
-// mpo_pop_train_step enqueues them (the side-stream form unless the plan is serial).
-void step_work(const Plan& P, long long* items, long long* launches) {
-    long long it = 0, ln = 0;
-    if (P.na > 0) {
-        auto one = [&](long long blocks) { if (blocks > 0) { it += blocks; ++ln; } };
-        auto segs = [&](const Bucketed& bk) { for (const Seg& sg : bk.segs) one(sg.end - sg.begin); };
-        one(64LL * P.na);                                  // flip_w2
-        segs(P.bc1); segs(P.bc2);
-        one((long long)P.per_sample.size());               // pool_fwd
-        one((long long)P.d1f.size()); one((long long)P.d2f.size());
-        one(P.na);                                         // softmax_bce
-        one((long long)P.d2w.size()); one((long long)P.d2d.size());
-        one((long long)P.d1w.size()); one((long long)P.d1d.size());
-        one((long long)P.per_sample.size());               // pool_bwd
-        segs(P.bdf); segs(P.bdg); segs(P.bw2); segs(P.bw1);
-        if (P.side.enabled && !P.timer.on) { one((long long)P.wred_blocks * P.na); one((long long)P.wred_blocks * P.na); }
-        else one(2LL * P.wred_blocks * P.na);              // wgrad_reduce
-        one((long long)P.colsum.size());
-        one((long long)P.adam.size());
-    }
-    *items = it;
-    *launches = ln;
 }
 
 int build_plan(Plan& P, const MpoCnnSpec* specs, int n, int B) {
@@ -1827,7 +1814,7 @@ int build_plan(Plan& P, const MpoCnnSpec* specs, int n, int B) {
     P.B = B;
     P.mem.resize(n);
     P.active.assign(n, 1);
-    Plan::FullLists& FL = P.full;
+    read_knobs(P);
     long long po = 0, ao = 0;
     auto palloc = [&](long long cnt) { long long o = po; po += (cnt + 63) / 64 * 64; return o; };
     auto aalloc = [&](long long cnt) { long long o = ao; ao += (cnt + 63) / 64 * 64; return o; };
@@ -1921,134 +1908,109 @@ int build_plan(Plan& P, const MpoCnnSpec* specs, int n, int B) {
     // r03: forward items of up to 256 pixels (4 m-tiles per wave) in <= 40 KiB (4 workgroups per CU) where
     // rows in [rmax/2, rmax] fit, else <= 100 KiB: conv2 fwd 9.66 -> 8.53 ms per 320-member batch
     // (profiles/r03/train_sweep_mt4_budget_am.log; 128-pixel items at 52/78 KiB were r01-r02's plan)
-    // r06, after dgfwd + wgpair (profiles/r06/mnist/av_*, aw_*): a 30 KiB first budget, 37.41 / 37.28 ->
-    // 37.13 / 37.08 ms per 320-member step, 3.95 -> 3.86 ms at 40, 1.633 -> 1.642 at 20 (24 and 36 alike)
-    const int kc1 = plan_knob("conv_kb1", 30), kc2 = plan_knob("conv_kb2", 100);
-    const int kdg = plan_knob("dg_kb", 78);
-    for (auto* v : {&P.L1, &P.L2, &P.LD, &P.LDF, &P.LW1, &P.LW2}) v->assign(n, 0);   // per-member LDS bytes per op
-    auto &L1 = P.L1, &L2 = P.L2, &LD = P.LD, &LDF = P.LDF, &LW1 = P.LW1, &LW2 = P.LW2;
+    for_each_list(P, [&](auto& L) { if (L.bucketed) L.lds.assign(n, 0); });
     for (int i = 0; i < n; ++i) {
         const Member& m = P.mem[i];
         const int k = m.k, F = m.F, nt = m.nt;
-        if (i == 0) P.conv_mt = plan_knob("conv_mt", 4) == 2 ? 2 : 4;
-        if (i == 0) P.side.enabled = plan_knob("streams", 3) >= 2;
-        if (i == 0) P.side2.enabled = plan_knob("streams", 3) >= 3;
-        if (i == 0) P.side2.slot = 1;
-        if (i == 0) P.side3.enabled = P.side.enabled && plan_knob("wgs", 2) >= 2;
-        if (i == 0) P.side3.slot = 2;
-        if (i == 0) P.side4.enabled = P.side2.enabled && plan_knob("dgs", 3) >= 3;
-        if (i == 0) P.side4.slot = 3;
+        const int kc1 = P.conv_kb1, kc2 = P.conv_kb2;
         const int mcap = P.conv_mt * 64;   // 4 waves x conv_mt m-tiles of 16 pixels
-        const int R1 = choose_rows(m.H1, [&](int R) { return conv_lds_bytes(R + k - 1, kImg, 1, m.H1, k * k, nt); }, kc1, kc2, mcap);
-        const int R2 = choose_rows(m.H2, [&](int R) { return conv_lds_bytes(R + k - 1, m.H1, F, m.H2, k * k * F, nt); }, kc1, kc2, mcap);
+        const int R1 = choose_rows(m.H1, [&](int R) { return conv_lds_bytes(R + k - 1, kImg, 1, m.H1, k * k); }, kc1, kc2, mcap);
+        const int R2 = choose_rows(m.H2, [&](int R) { return conv_lds_bytes(R + k - 1, m.H1, F, m.H2, k * k * F); }, kc1, kc2, mcap);
         // dgrad: 4x4-pixel tiles in bands of 4 rows, <= 16 tiles (4 per wave) per chunk:
         // R = 4 * floor(16 / CT); 4-row bands fewer if the LDS budget asks for it
-        const size_t dgb = (size_t)kdg << 10;
-        // r03: at most 12 tiles (3 per wave): conv2 dgrad 15.40 -> 15.15 ms per 320-member batch
-        // (profiles/r03/train_sweep_dgtiles_ap.log; 16 was r01-r02's, 8 measured 16.96)
-        if (i == 0) P.dg_tiles = std::max(1, std::min(16, plan_knob("dg_tiles", 12)));
+        const size_t dgb = (size_t)P.dg_kb << 10;
         int Rd = 4 * std::max(1, P.dg_tiles / ((m.H1 + 3) / 4));
         while (Rd > 4 && dgrad_lds_bytes(Rd, k, F, m.H2) > dgb) Rd -= 4;
-        const size_t l1 = conv_lds_bytes(R1 + k - 1, kImg, 1, m.H1, k * k, nt);
-        const size_t l2 = conv_lds_bytes(R2 + k - 1, m.H1, F, m.H2, k * k * F, nt);
+        const size_t l1 = conv_lds_bytes(R1 + k - 1, kImg, 1, m.H1, k * k);
+        const size_t l2 = conv_lds_bytes(R2 + k - 1, m.H1, F, m.H2, k * k * F);
         size_t ld = dgrad_lds_bytes(Rd, k, F, m.H2);
         // the zero-bordered forward formulation (k small: (H1 / H2)^2 of padded work)
         // r06, MI355X, 320 members (profiles/r06/mnist/ao_*, ap_*): k <= 4 -> 36.70 ms per train step
         // 35.85 (k = 4 carries it; k = 2-3 neutral), with an 80 KiB first LDS budget 35.67; adding k =
         // 5..10 one at a time: 5-7 within noise, 8 +0.2, 9 +0.6, 10 +2.2 ms.  Bits unchanged.
-        if (i == 0) P.dgfwd = plan_knob("dgfwd", 4);
-        if (i == 0) P.dgfset = plan_knob("dgfset", 0);
         const bool fwd_dg = k <= P.dgfwd || ((P.dgfset >> k) & 1);
         const int F4 = (F + 3) & ~3, Hp = m.H1 + k - 1;
-        const int Rf = choose_rows(m.H1, [&](int R) { return conv_lds_bytes(R + k - 1, Hp, F4, m.H1, k * k * F4, nt); },
-                                   plan_knob("dgf_kb1", 80), plan_knob("dgf_kb2", kc2), mcap);
-        if (fwd_dg) ld = conv_lds_bytes(Rf + k - 1, Hp, F4, m.H1, k * k * F4, nt);
-        L1[i] = l1; L2[i] = l2; LD[i] = ld; LDF[i] = ld;
+        const int Rf = choose_rows(m.H1, [&](int R) { return conv_lds_bytes(R + k - 1, Hp, F4, m.H1, k * k * F4); },
+                                   P.dgf_kb1, P.dgf_kb2, mcap);
+        if (fwd_dg) ld = conv_lds_bytes(Rf + k - 1, Hp, F4, m.H1, k * k * F4);
+        P.conv1.lds[i] = l1; P.conv2.lds[i] = l2; P.dgrad.lds[i] = ld; P.dgf.lds[i] = ld;
         for (int b = 0; b < B; ++b) {
-            for (int y = 0; y < m.H1; y += R1) FL.conv1.push_back({i, b, y, std::min(R1, m.H1 - y)});
-            for (int y = 0; y < m.H2; y += R2) FL.conv2.push_back({i, b, y, std::min(R2, m.H2 - y)});
+            for (int y = 0; y < m.H1; y += R1) P.conv1.full.push_back({i, b, y, std::min(R1, m.H1 - y)});
+            for (int y = 0; y < m.H2; y += R2) P.conv2.full.push_back({i, b, y, std::min(R2, m.H2 - y)});
             if (fwd_dg)
-                for (int y = 0; y < m.H1; y += Rf) FL.dgf.push_back({i, b, y, std::min(Rf, m.H1 - y)});
+                for (int y = 0; y < m.H1; y += Rf) P.dgf.full.push_back({i, b, y, std::min(Rf, m.H1 - y)});
             else
-                for (int y = 0; y < m.H1; y += Rd) FL.dgrad.push_back({i, b, y, std::min(Rd, m.H1 - y)});
-            FL.per_sample.push_back({i, b});
+                for (int y = 0; y < m.H1; y += Rd) P.dgrad.full.push_back({i, b, y, std::min(Rd, m.H1 - y)});
+            P.per_sample.full.push_back({i, b});
         }
         P.lds_conv_max = std::max({P.lds_conv_max, l1, l2, ld});
         // wgrad items: (member, 512-row m-group, sample group)
-        if (i == 0) P.wgrpb = plan_knob("wgrpb", 2) == 1 ? 1 : 2;
-        // r06, MI355X (profiles/r06/mnist/as_*.log): 37.70 -> 37.29 ms per 320-member step,
-        // 1.64 -> 1.63 ms at 20; losses bit-identical (a padding pixel's MFMA product is an exact zero)
-        if (i == 0) P.wgpair = plan_knob("wgpair", 1);
         const size_t lw2 = wg_lds_bytes(k, m.H1, F, m.H2, F, P.wgrpb);
-        const size_t lw1 = wg_lds_bytes(k, kImg, 1, m.H1, F);
-        LW2[i] = lw2; LW1[i] = lw1;
         const int K2 = k * k * F, K1w = k * k;
         for (int g = 0; g < m.g2; ++g) {
             const int b0 = (int)((long long)B * g / m.g2), b1 = (int)((long long)B * (g + 1) / m.g2);
-            for (int mg = 0; mg * kWgRows <= K2; ++mg) FL.wg2.push_back({i, mg, b0, b1, g, wg_mt(K2, mg)});
+            for (int mg = 0; mg * kWgRows <= K2; ++mg) P.wg2.full.push_back({i, mg, b0, b1, g, wg_mt(K2, mg)});
         }
         // conv1_wgrad_kernel: every m-tile in one wave, MT bucketed to 1, 2, 4 or 7
         const int t1 = (K1w + 1 + 15) / 16, mt1 = t1 <= 1 ? 1 : t1 <= 2 ? 2 : t1 <= 4 ? 4 : 7;
-        LW1[i] = (size_t)w1_lds_floats((B + m.g1 - 1) / m.g1, mt1, nt) * sizeof(float);
+        const size_t lw1 = (size_t)w1_lds_floats((B + m.g1 - 1) / m.g1, mt1, nt) * sizeof(float);
         for (int g = 0; g < m.g1; ++g) {
             const int b0 = (int)((long long)B * g / m.g1), b1 = (int)((long long)B * (g + 1) / m.g1);
-            FL.wg1.push_back({i, 0, b0, b1, g, mt1});
+            P.wg1.full.push_back({i, 0, b0, b1, g, mt1});
         }
+        P.wg2.lds[i] = lw2; P.wg1.lds[i] = lw1;
         P.lds_wg_max = std::max({P.lds_wg_max, lw2, lw1});
-        auto tiles = [&](std::vector<GemmItem>& v, int M, int N) {
+        auto tiles = [&](WorkList<GemmItem>& L, int M, int N) {
             for (int m0 = 0; m0 < M; m0 += 64)
-                for (int n0 = 0; n0 < N; n0 += 64) v.push_back({i, m0, n0, 0});
+                for (int n0 = 0; n0 < N; n0 += 64) L.full.push_back({i, m0, n0, 0});
         };
-        tiles(FL.d1f, B, m.dense);
-        tiles(FL.d2f, B, kClasses);
-        tiles(FL.d2w, m.dense, kClasses);
-        tiles(FL.d2d, B, m.dense);
-        tiles(FL.d1w, m.K1, m.dense);
-        tiles(FL.d1d, B, m.K1);
-        FL.per_member.push_back({i, 0});
-        for (int c = 2; c < 4; ++c) FL.colsum.push_back({i, c});
+        tiles(P.d1f, B, m.dense);
+        tiles(P.d2f, B, kClasses);
+        tiles(P.d2w, m.dense, kClasses);
+        tiles(P.d2d, B, m.dense);
+        tiles(P.d1w, m.K1, m.dense);
+        tiles(P.d1d, B, m.K1);
+        P.per_member.full.push_back({i, 0});
+        for (int c = 2; c < 4; ++c) P.colsum.full.push_back({i, c});
         const long long np_ = m.pend - m.w1;
-        for (long long c = 0; c * P.adam_chunk < np_; ++c) FL.adam.push_back({i, (int)c});
+        for (long long c = 0; c * P.adam_chunk < np_; ++c) P.adam.full.push_back({i, (int)c});
     }
     if (P.lds_conv_max > 160 * 1024 || P.lds_wg_max > 160 * 1024) {
         mpo::set_error("mpo_pop_create: LDS plan exceeds 160 KiB (conv %zu, wgrad %zu)", P.lds_conv_max, P.lds_wg_max);
         return MPO_ENOTSUP;
     }
-    // Small populations (a distributed shard, configs[0]) launch too few workgroups per occupancy class
-    // to fill the chip.  Merging every class of an (NT, sub) bucket (mode 1) measured on MI355X
-    // (profiles/r05/occmerge_o.log): 20 members 3.82 -> 3.52 ms, 40: 5.93 -> 5.70, 80: 10.94 -> 10.96,
-    // 160: 19.81 -> 20.30, 320: 36.92 -> 39.06 ms per train step.  Merging only adjacent classes
-    // short of one full wave (mode 2, the default): 20: 3.53, 40: 5.56-5.59, 80: 10.63-10.67,
-    // 320: 36.81-36.95 (separate classes 36.87) -- profiles/r05/occmerge2_*.log.  The segmenting
-    // changes no arithmetic.
-    P.occmerge = plan_knob("occmerge", 2);
-    P.xcd = plan_knob("xcd", 4);
     apply_mask(P);
     write_tables(P, true);
     return MPO_OK;
 }
 
 template <class T>
-const T* dev_table(const Plan& P, size_t off) {
-    return reinterpret_cast<const T*>(P.table_base + off);
+const T* dev_table(const Plan& P, const WorkList<T>& L) {
+    return reinterpret_cast<const T*>(P.table_base + L.off);
+}
+
+// Every launch of a step goes through MPO_TALLY_LAUNCH, so that mpo_pop_step_work can
+// walk the step (mpo::Tally); the other HIP calls on that path are skipped under a tally.
+// One segment of a bucketed list: a block per item, `lds` bytes of dynamic LDS.
+template <class Kern, class T>
+hipError_t launch_items(Kern kern, unsigned threads, const StepArgs& a, const T* items, int count, size_t lds,
+                        hipStream_t s) {
+    if (count <= 0) return hipSuccess;
+    if (!mpo::g_tally)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    MPO_TALLY_LAUNCH(kern, dim3(count), dim3(threads), lds, s, a, items);
+    return mpo::tally_launch_error();
 }
 
 template <int OP, int NT>
 hipError_t launch_conv_nt(const StepArgs& a, const ConvItem* items, int count, size_t lds, hipStream_t s) {
-    if (count <= 0) return hipSuccess;
     auto kern = a.conv_mt == 4 ? conv_img_kernel<OP, NT, 4> : conv_img_kernel<OP, NT, 2>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(count), dim3(256), lds, s, a, items);
-    return hipGetLastError();
+    return launch_items(kern, 256, a, items, count, lds, s);
 }
 
 template <int NT>
 hipError_t launch_dgrad_nt(const StepArgs& a, const ConvItem* items, int count, size_t lds, hipStream_t s) {
-    if (count <= 0) return hipSuccess;
-    auto kern = conv_dgrad_kernel<NT>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(count), dim3(256), lds, s, a, items);
-    return hipGetLastError();
+    return launch_items(conv_dgrad_kernel<NT>, 256, a, items, count, lds, s);
 }
 
 template <int OP, int NT, int RPB>
@@ -2059,36 +2021,33 @@ auto wg_kernel(int mt) {
 
 template <int OP, int NT>
 hipError_t launch_wg_nt(const StepArgs& a, const WgItem* items, int count, size_t lds, int mt, hipStream_t s) {
-    if (count <= 0) return hipSuccess;
     auto kern = a.wgrpb == 2 ? wg_kernel<OP, NT, 2>(mt) : wg_kernel<OP, NT, 1>(mt);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(count), dim3(kWgThreads), lds, s, a, items);
-    return hipGetLastError();
+    return launch_items(kern, kWgThreads, a, items, count, lds, s);
 }
 
 template <int NT>
 hipError_t launch_wg1_wave_nt(const StepArgs& a, const WgItem* items, int count, size_t lds, int mt, hipStream_t s) {
-    if (count <= 0) return hipSuccess;
     auto kern = mt == 1 ? conv1_wgrad_kernel<NT, 1> : mt == 2 ? conv1_wgrad_kernel<NT, 2>
               : mt == 4 ? conv1_wgrad_kernel<NT, 4> : conv1_wgrad_kernel<NT, 7>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL(kern, dim3(count), dim3(kW1Waves * 64), lds, s, a, items);
-    return hipGetLastError();
+    return launch_items(kern, kW1Waves * 64, a, items, count, lds, s);
 }
 
-// s2 (optional): segments alternate between s and s2 (independent launches)
-template <class Fn>
-hipError_t launch_segs(Plan& P, const Bucketed& bk, const char* name, hipStream_t s, Fn launch_nt,
-                       hipStream_t s2 = nullptr, hipStream_t s3 = nullptr) {
+// One launch per segment of a bucketed list: launch_nt(device items, count, segment, stream).
+// s2 (, s3) (optional): segments alternate between s and s2 (, s3) (independent launches)
+template <class T, class Fn>
+hipError_t launch_segs(Plan& P, const WorkList<T>& L, hipStream_t s, Fn launch_nt, hipStream_t s2 = nullptr,
+                       hipStream_t s3 = nullptr) {
+    const T* base = dev_table(P, L);
     // segments dealt round-robin over s, s2 (, s3)
     const hipStream_t st[3] = {s, s2, s3};
     const int ns = s2 ? (s3 ? 3 : 2) : 1;
     int i = 0;
-    for (const Seg& sg : bk.segs) {
-        if (hipError_t e = launch_nt(sg, st[i++ % ns])) return e;
-        P.timer.mark(std::string(name) + "/nt" + std::to_string(sg.nt) + (sg.sub ? "/mt" + std::to_string(sg.sub) : "") +
-                         (P.timer_detail ? "/occ" + std::to_string(lds_class(sg.lds)) + "/n" + std::to_string(sg.end - sg.begin) : ""),
-                     s);
+    for (const Seg& sg : L.segs) {
+        if (hipError_t e = launch_nt(base + sg.begin, sg.end - sg.begin, sg, st[i++ % ns])) return e;
+        if (P.timer.live())
+            P.timer.mark(std::string(L.name) + "/nt" + std::to_string(sg.nt) + (sg.sub ? "/mt" + std::to_string(sg.sub) : "") +
+                             (P.timer_detail ? "/occ" + std::to_string(lds_class(sg.lds)) + "/n" + std::to_string(sg.end - sg.begin) : ""),
+                         s);
     }
     return hipSuccess;
 }
@@ -2107,23 +2066,18 @@ struct ConvLaunch {
 };
 
 template <int OP>
-hipError_t launch_conv(Plan& P, const StepArgs& a, size_t table_off, const Bucketed& bk, hipStream_t s,
-                       hipStream_t s2 = nullptr) {
-    const ConvItem* base = dev_table<ConvItem>(P, table_off);
-    return launch_segs(P, bk, OP == CONV1_FWD ? "conv1_fwd" : "conv2_fwd", s, [&](const Seg& sg, hipStream_t st) {
-        return MPO_NT_SWITCH(ConvLaunch<OP>::template go, sg, a, base + sg.begin, sg.end - sg.begin, sg.lds, st);
-    }, s2);
+hipError_t launch_conv(Plan& P, const StepArgs& a, const WorkList<ConvItem>& L, hipStream_t s,
+                       hipStream_t s2 = nullptr, hipStream_t s3 = nullptr) {
+    return launch_segs(P, L, s, [&](const ConvItem* items, int count, const Seg& sg, hipStream_t st) {
+        return MPO_NT_SWITCH(ConvLaunch<OP>::template go, sg, a, items, count, sg.lds, st);
+    }, s2, s3);
 }
 
+// the conv2 input gradient: the zero-bordered forward conv's members, then the gather kernel's
 hipError_t launch_dgrad(Plan& P, const StepArgs& a, hipStream_t s, hipStream_t s2 = nullptr, hipStream_t s3 = nullptr) {
-    const ConvItem* base = dev_table<ConvItem>(P, P.off_dgrad);
-    const ConvItem* fbase = dev_table<ConvItem>(P, P.off_dgf);
-    if (hipError_t e = launch_segs(P, P.bdf, "conv2_dgrad_fwd", s, [&](const Seg& sg, hipStream_t st) {
-            return MPO_NT_SWITCH(ConvLaunch<CONV2_DGRAD>::template go, sg, a, fbase + sg.begin, sg.end - sg.begin, sg.lds, st);
-        }, s2, s3))
-        return e;
-    return launch_segs(P, P.bdg, "conv2_dgrad", s, [&](const Seg& sg, hipStream_t st) {
-        return MPO_NT_SWITCH(launch_dgrad_nt, sg, a, base + sg.begin, sg.end - sg.begin, sg.lds, st);
+    if (hipError_t e = launch_conv<CONV2_DGRAD>(P, a, P.dgf, s, s2, s3)) return e;
+    return launch_segs(P, P.dgrad, s, [&](const ConvItem* items, int count, const Seg& sg, hipStream_t st) {
+        return MPO_NT_SWITCH(launch_dgrad_nt, sg, a, items, count, sg.lds, st);
     }, s2, s3);
 }
 
@@ -2136,28 +2090,27 @@ struct WgLaunch {
 };
 
 template <int OP>
-hipError_t launch_wg(Plan& P, const StepArgs& a, size_t table_off, const Bucketed& bk, hipStream_t s,
-                     hipStream_t s_alt = nullptr) {
-    const WgItem* base = dev_table<WgItem>(P, table_off);
-    return launch_segs(P, bk, OP == WG_CONV1 ? "conv1_wgrad" : "conv2_wgrad", s, [&](const Seg& sg, hipStream_t st) {
+hipError_t launch_wg(Plan& P, const StepArgs& a, const WorkList<WgItem>& L, hipStream_t s, hipStream_t s_alt = nullptr) {
+    return launch_segs(P, L, s, [&](const WgItem* items, int count, const Seg& sg, hipStream_t st) {
         if constexpr (OP == WG_CONV1)
-            return MPO_NT_SWITCH(launch_wg1_wave_nt, sg, a, base + sg.begin, sg.end - sg.begin, sg.lds, sg.sub, st);
+            return MPO_NT_SWITCH(launch_wg1_wave_nt, sg, a, items, count, sg.lds, sg.sub, st);
         else
-            return MPO_NT_SWITCH(WgLaunch<OP>::template go, sg, a, base + sg.begin, sg.end - sg.begin, sg.lds, sg.sub, st);
+            return MPO_NT_SWITCH(WgLaunch<OP>::template go, sg, a, items, count, sg.lds, sg.sub, st);
     }, s_alt);
 }
 
-template <int OP>
-hipError_t launch_dense(const Plan& P, const StepArgs& a, size_t off, size_t count, hipStream_t s) {
-    if (!count) return hipSuccess;
-    hipLaunchKernelGGL(dense_kernel<OP>, dim3((unsigned)count), dim3(256), 0, s, a, dev_table<GemmItem>(P, off));
-    return hipGetLastError();
+// One launch over a whole unbucketed list, a block per item.
+template <class Kern, class T, class... Extra>
+hipError_t launch_list(Kern kern, const Plan& P, const StepArgs& a, const WorkList<T>& L, hipStream_t s, Extra... extra) {
+    if (!L.size()) return hipSuccess;
+    MPO_TALLY_LAUNCH(kern, dim3((unsigned)L.size()), dim3(256), 0, s, a, dev_table(P, L), extra...);
+    return mpo::tally_launch_error();
 }
 
 StepArgs make_args(const Plan& P, const float* x, const int* labels, const int* order, long long order_stride,
                    long long row0, int step, int train) {
     StepArgs a;
-    a.mem = dev_table<Member>(P, P.off_mem);
+    a.mem = reinterpret_cast<const Member*>(P.table_base + P.off_mem);
     a.params = P.params;
     a.grads = P.grads;
     a.act = P.act;
@@ -2180,30 +2133,117 @@ StepArgs make_args(const Plan& P, const float* x, const int* labels, const int* 
     return a;
 }
 
+// One side stream in one step.  `on`: whether the step forks onto it, which is the plan's
+// decision (enabled, and profiled steps stay serial): a tally walk obtains no stream and
+// makes no HIP call, yet takes the branches of the real step.  A real step also needs
+// the stream `st` itself; where it cannot be created, SideStream::get disables the side
+// stream for good, and this and every later step, walked or real, is serial there.
+struct Side {
+    mpo::SideStream& ss;
+    bool on;
+    hipStream_t st = nullptr;
+    Side(Plan& P, mpo::SideStream& ss_, hipStream_t s, bool wanted = true)
+        : ss(ss_), on(wanted && ss_.enabled && !P.timer.on) {
+        if (on && !mpo::g_tally) on = (st = ss.get(s)) != nullptr;
+    }
+    // `st` starts after everything enqueued on `from` so far / `into` continues after `st`
+    hipError_t fork(hipStream_t from) { return mpo::g_tally ? hipSuccess : ss.fork(from, st); }
+    hipError_t join(hipStream_t into) { return mpo::g_tally ? hipSuccess : ss.join(into, st); }
+};
+
 int forward(Plan& P, const StepArgs& a, hipStream_t s) {
     P.timer.mark("start", s);
     // padded / rotated weight copies for this step's convolutions
-    hipLaunchKernelGGL(flip_w2_kernel, dim3(64, (unsigned)P.na), dim3(256), 0, s, a, dev_table<MItem>(P, P.off_pm));
-    MPO_LAUNCH_CHECK();
+    MPO_TALLY_LAUNCH(flip_w2_kernel, dim3(64, (unsigned)P.na), dim3(256), 0, s, a, dev_table(P, P.per_member));
+    MPO_TALLY_LAUNCH_CHECK();
     P.timer.mark("flip_w2", s);
-    MPO_HIP(launch_conv<CONV1_FWD>(P, a, P.off_conv1, P.bc1, s));
-    if (hipStream_t s2 = P.timer.on ? nullptr : P.side.get(s)) {   // profiled steps stay serial
-        MPO_HIP(P.side.fork(s, s2));
-        MPO_HIP(launch_conv<CONV2_FWD>(P, a, P.off_conv2, P.bc2, s, s2));
-        MPO_HIP(P.side.join(s, s2));
+    MPO_HIP(launch_conv<CONV1_FWD>(P, a, P.conv1, s));
+    Side wg(P, P.side_wg, s);
+    if (wg.on) {
+        MPO_HIP(wg.fork(s));
+        MPO_HIP(launch_conv<CONV2_FWD>(P, a, P.conv2, s, wg.st));
+        MPO_HIP(wg.join(s));
     } else {
-        MPO_HIP(launch_conv<CONV2_FWD>(P, a, P.off_conv2, P.bc2, s));
+        MPO_HIP(launch_conv<CONV2_FWD>(P, a, P.conv2, s));
     }
-    hipLaunchKernelGGL(pool_fwd_kernel, dim3((unsigned)P.per_sample.size()), dim3(256), 0, s, a,
-                       dev_table<MItem>(P, P.off_ps));
-    MPO_LAUNCH_CHECK();
+    MPO_HIP(launch_list(pool_fwd_kernel, P, a, P.per_sample, s));
     P.timer.mark("pool_fwd", s);
-    MPO_HIP(launch_dense<D1_FWD>(P, a, P.off_d1f, P.d1f.size(), s));
-    MPO_HIP(launch_dense<D2_FWD>(P, a, P.off_d2f, P.d2f.size(), s));
+    MPO_HIP(launch_list(dense_kernel<D1_FWD>, P, a, P.d1f, s));
+    MPO_HIP(launch_list(dense_kernel<D2_FWD>, P, a, P.d2f, s));
     P.timer.mark("dense_fwd", s);
-    hipLaunchKernelGGL(softmax_bce_kernel, dim3((unsigned)P.na), dim3(256), 0, s, a, dev_table<MItem>(P, P.off_pm));
-    MPO_LAUNCH_CHECK();
+    MPO_HIP(launch_list(softmax_bce_kernel, P, a, P.per_member, s));
     P.timer.mark("softmax_bce", s);
+    return MPO_OK;
+}
+
+// The launches of one train step (a: make_args with train = 1 and loss_out set), which
+// mpo_pop_train_step enqueues and mpo_pop_step_work walks under a tally.
+int enqueue_train(Plan& P, const StepArgs& a, hipStream_t s) {
+    if (P.na == 0) return MPO_OK;   // every member retired: nothing to launch
+    int rc = forward(P, a, s);
+    if (rc) return rc;
+    // backward.  With the side stream s2: each weight gradient runs on s2 beside the
+    // input gradient that follows it on s (disjoint outputs; s2 stays one stream, so
+    // its work keeps its own order), the conv2 slab reduction right after the conv2
+    // weight gradient, and s joins s2 before Adam.
+    Side wg(P, P.side_wg, s);
+    const hipStream_t s2 = wg.st;
+    const MItem* wred = dev_table(P, P.wred);
+    const unsigned nm = (unsigned)P.na;   // the wred halves: items [0, na) conv2, [na, 2 na) conv1
+    const dim3 wred_grid((unsigned)P.wred_blocks, nm);
+    if (wg.on) {
+        MPO_HIP(wg.fork(s));                                                // dz3 ready
+        MPO_HIP(launch_list(dense_kernel<D2_WGRAD>, P, a, P.d2w, s2));
+        MPO_HIP(launch_list(dense_kernel<D2_DGRAD>, P, a, P.d2d, s));
+        MPO_HIP(wg.fork(s));                                                // dh ready
+        MPO_HIP(launch_list(dense_kernel<D1_WGRAD>, P, a, P.d1w, s2));
+        MPO_HIP(launch_list(dense_kernel<D1_DGRAD>, P, a, P.d1d, s));
+    } else {
+        MPO_HIP(launch_list(dense_kernel<D2_WGRAD>, P, a, P.d2w, s));
+        MPO_HIP(launch_list(dense_kernel<D2_DGRAD>, P, a, P.d2d, s));
+        MPO_HIP(launch_list(dense_kernel<D1_WGRAD>, P, a, P.d1w, s));
+        MPO_HIP(launch_list(dense_kernel<D1_DGRAD>, P, a, P.d1d, s));
+    }
+    P.timer.mark("dense_bwd", s);
+    MPO_HIP(launch_list(pool_bwd_kernel, P, a, P.per_sample, s));
+    P.timer.mark("pool_bwd", s);
+    if (wg.on) {
+        // conv2 weight gradient (a1, dz2 -> slabs -> dw2) beside the input gradient and
+        // the conv1 weight gradient (dz2 -> dz1 -> slabs -> dw1): disjoint outputs
+        MPO_HIP(wg.fork(s));                                                // dz2 ready
+        Side wg_alt(P, P.side_wg_alt, s);   // disjoint slab rows per bucket: alternating buckets may overlap
+        if (wg_alt.on) MPO_HIP(wg_alt.fork(s));
+        MPO_HIP(launch_wg<WG_CONV2>(P, a, P.wg2, s2, wg_alt.st));
+        if (wg_alt.on) MPO_HIP(wg_alt.join(s2));                            // the slab reduction reads all of them
+        MPO_TALLY_LAUNCH(wgrad_reduce_kernel, wred_grid, dim3(256), 0, s2, a, wred, P.wred_per_block);
+        MPO_TALLY_LAUNCH_CHECK();
+        Side dg(P, P.side_dg, s);           // input-gradient buckets over s and dg.st (disjoint rows of dz1)
+        if (dg.on) {
+            MPO_HIP(dg.fork(s));
+            Side dg_alt(P, P.side_dg_alt, s);
+            if (dg_alt.on) MPO_HIP(dg_alt.fork(s));
+            MPO_HIP(launch_dgrad(P, a, s, dg.st, dg_alt.st));
+            MPO_HIP(dg.join(s));
+            if (dg_alt.on) MPO_HIP(dg_alt.join(s));
+        } else {
+            MPO_HIP(launch_dgrad(P, a, s));
+        }
+        MPO_HIP(launch_wg<WG_CONV1>(P, a, P.wg1, s));
+        MPO_TALLY_LAUNCH(wgrad_reduce_kernel, wred_grid, dim3(256), 0, s, a, wred + nm, P.wred_per_block);
+        MPO_TALLY_LAUNCH_CHECK();
+        MPO_HIP(wg.join(s));
+    } else {
+        MPO_HIP(launch_dgrad(P, a, s));
+        MPO_HIP(launch_wg<WG_CONV2>(P, a, P.wg2, s));
+        MPO_HIP(launch_wg<WG_CONV1>(P, a, P.wg1, s));
+        MPO_TALLY_LAUNCH(wgrad_reduce_kernel, dim3((unsigned)P.wred_blocks, 2 * nm), dim3(256), 0, s, a, wred,
+                         P.wred_per_block);
+        MPO_TALLY_LAUNCH_CHECK();
+    }
+    MPO_HIP(launch_list(colsum_kernel, P, a, P.colsum, s));
+    P.timer.mark("wgrad_reduce", s);
+    MPO_HIP(launch_list(adam_kernel, P, a, P.adam, s, P.params, P.m, P.v, a.step + 1, 0.9f, 0.999f, 1e-8f, P.adam_chunk));
+    P.timer.mark("adam", s);
     return MPO_OK;
 }
 
@@ -2304,12 +2344,28 @@ int mpo_pop_set_active(void* handle, const uint8_t* active, void* stream) {
 }
 
 int mpo_pop_step_work(const void* handle, int64_t* items, int64_t* launches) {
+    MPO_GUARD_BEGIN
     MPO_CHECK_ARG(handle && items && launches, "mpo_pop_step_work: null pointer");
-    long long it = 0, ln = 0;
-    step_work(*static_cast<const Plan*>(handle), &it, &ln);
-    *items = it;
-    *launches = ln;
+    // the plan is only read: the tally makes every launch site count instead of launch.
+    // The walk runs on stand-in pointers (offsets are added to them, nothing is
+    // dereferenced), an unbound plan's table region included.
+    Plan& P = *const_cast<Plan*>(static_cast<const Plan*>(handle));
+    alignas(256) static float stand_in[64];
+    char* const tables = P.table_base;
+    if (!P.bound) P.table_base = reinterpret_cast<char*>(stand_in);
+    StepArgs a = make_args(P, stand_in, reinterpret_cast<const int*>(stand_in), reinterpret_cast<const int*>(stand_in),
+                           P.B, 0, 0, 1);
+    a.loss_out = stand_in;
+    mpo::Tally t;
+    mpo::g_tally = &t;
+    const int rc = enqueue_train(P, a, nullptr);
+    mpo::g_tally = nullptr;
+    P.table_base = tables;
+    if (rc != MPO_OK) return rc;
+    *items = t.workgroups;
+    *launches = t.launches;
     return MPO_OK;
+    MPO_GUARD_END
 }
 
 int mpo_pop_train_step(void* handle, const float* x, const int32_t* labels, const int32_t* order, int64_t order_stride,
@@ -2319,78 +2375,10 @@ int mpo_pop_train_step(void* handle, const float* x, const int32_t* labels, cons
     Plan& P = *static_cast<Plan*>(handle);
     MPO_CHECK_ARG(P.bound, "mpo_pop_train_step: call mpo_pop_bind first");
     MPO_CHECK_ARG(step >= 0, "mpo_pop_train_step: step must be >= 0");
-    if (P.na == 0) return MPO_OK;   // every member retired: nothing to launch
-    hipStream_t s = static_cast<hipStream_t>(stream);
     StepArgs a = make_args(P, x, labels, order, order_stride, row0, step, 1);
     a.loss_out = loss_out;
-    int rc = forward(P, a, s);
+    const int rc = enqueue_train(P, a, static_cast<hipStream_t>(stream));
     if (rc) return rc;
-    // backward.  With the side stream s2: each weight gradient runs on s2 beside the
-    // input gradient that follows it on s (disjoint outputs; s2 stays one stream, so
-    // its work keeps its own order), the conv2 slab reduction right after the conv2
-    // weight gradient, and s joins s2 before Adam.
-    hipStream_t s2 = P.timer.on ? nullptr : P.side.get(s);
-    const MItem* wred = dev_table<MItem>(P, P.off_wr);
-    const unsigned nm = (unsigned)P.na;   // the wred halves: items [0, na) conv2, [na, 2 na) conv1
-    if (s2) {
-        MPO_HIP(P.side.fork(s, s2));                                        // dz3 ready
-        MPO_HIP(launch_dense<D2_WGRAD>(P, a, P.off_d2w, P.d2w.size(), s2));
-        MPO_HIP(launch_dense<D2_DGRAD>(P, a, P.off_d2d, P.d2d.size(), s));
-        MPO_HIP(P.side.fork(s, s2));                                        // dh ready
-        MPO_HIP(launch_dense<D1_WGRAD>(P, a, P.off_d1w, P.d1w.size(), s2));
-        MPO_HIP(launch_dense<D1_DGRAD>(P, a, P.off_d1d, P.d1d.size(), s));
-    } else {
-        MPO_HIP(launch_dense<D2_WGRAD>(P, a, P.off_d2w, P.d2w.size(), s));
-        MPO_HIP(launch_dense<D2_DGRAD>(P, a, P.off_d2d, P.d2d.size(), s));
-        MPO_HIP(launch_dense<D1_WGRAD>(P, a, P.off_d1w, P.d1w.size(), s));
-        MPO_HIP(launch_dense<D1_DGRAD>(P, a, P.off_d1d, P.d1d.size(), s));
-    }
-    P.timer.mark("dense_bwd", s);
-    hipLaunchKernelGGL(pool_bwd_kernel, dim3((unsigned)P.per_sample.size()), dim3(256), 0, s, a,
-                       dev_table<MItem>(P, P.off_ps));
-    MPO_LAUNCH_CHECK();
-    P.timer.mark("pool_bwd", s);
-    if (s2) {
-        // conv2 weight gradient (a1, dz2 -> slabs -> dw2) beside the input gradient and
-        // the conv1 weight gradient (dz2 -> dz1 -> slabs -> dw1): disjoint outputs
-        MPO_HIP(P.side.fork(s, s2));                                        // dz2 ready
-        hipStream_t s4 = P.side3.get(s);   // disjoint slab rows per bucket: alternating buckets may overlap
-        if (s4) MPO_HIP(P.side3.fork(s, s4));
-        MPO_HIP(launch_wg<WG_CONV2>(P, a, P.off_wg2, P.bw2, s2, s4));
-        if (s4) MPO_HIP(P.side3.join(s2, s4));                              // the slab reduction reads all of them
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)P.wred_blocks, nm), dim3(256), 0, s2, a, wred,
-                           P.wred_per_block);
-        MPO_LAUNCH_CHECK();
-        if (hipStream_t s3 = P.side2.get(s)) {   // input-gradient buckets over s and s3 (disjoint rows of dz1)
-            MPO_HIP(P.side2.fork(s, s3));
-            hipStream_t s5 = P.side4.get(s);
-            if (s5) MPO_HIP(P.side4.fork(s, s5));
-            MPO_HIP(launch_dgrad(P, a, s, s3, s5));
-            MPO_HIP(P.side2.join(s, s3));
-            if (s5) MPO_HIP(P.side4.join(s, s5));
-        } else {
-            MPO_HIP(launch_dgrad(P, a, s));
-        }
-        MPO_HIP(launch_wg<WG_CONV1>(P, a, P.off_wg1, P.bw1, s));
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)P.wred_blocks, nm), dim3(256), 0, s, a, wred + nm,
-                           P.wred_per_block);
-        MPO_LAUNCH_CHECK();
-        MPO_HIP(P.side.join(s, s2));
-    } else {
-        MPO_HIP(launch_dgrad(P, a, s));
-        MPO_HIP(launch_wg<WG_CONV2>(P, a, P.off_wg2, P.bw2, s));
-        MPO_HIP(launch_wg<WG_CONV1>(P, a, P.off_wg1, P.bw1, s));
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)P.wred_blocks, 2 * nm), dim3(256), 0, s, a, wred,
-                           P.wred_per_block);
-        MPO_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(colsum_kernel, dim3((unsigned)P.colsum.size()), dim3(256), 0, s, a, dev_table<MItem>(P, P.off_cs));
-    MPO_LAUNCH_CHECK();
-    P.timer.mark("wgrad_reduce", s);
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)P.adam.size()), dim3(256), 0, s, a, dev_table<MItem>(P, P.off_adam),
-                       P.params, P.m, P.v, step + 1, 0.9f, 0.999f, 1e-8f, P.adam_chunk);
-    MPO_LAUNCH_CHECK();
-    P.timer.mark("adam", s);
     P.timer.finish();
     return MPO_OK;
     MPO_GUARD_END

@@ -1483,28 +1483,7 @@ __global__ void dn_adam_kernel(float* __restrict__ params, float* __restrict__ g
 enum Kind { K_CONV0 = 0, K_DENSE = 1, K_TRANS = 2, K_HEAD = 3 };
 
 // mpo_dn_step_work walks the enqueue functions of a train step with a tally set on its
-// thread: every launch adds its grid to the tally instead of running, so the figures
-// cannot drift from what a step launches.  No HIP call is made while a tally is set.
-struct Tally {
-    long long workgroups = 0, launches = 0;
-};
-thread_local Tally* g_tally = nullptr;
-
-#define DN_LAUNCH(kern, grid, block, lds, stream, ...)                           \
-    do {                                                                         \
-        if (g_tally) {                                                           \
-            const dim3 g_ = (grid);                                              \
-            g_tally->workgroups += (long long)g_.x * g_.y * g_.z;                \
-            ++g_tally->launches;                                                 \
-        } else {                                                                 \
-            hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);     \
-        }                                                                        \
-    } while (0)
-#define DN_LAUNCH_CHECK()                \
-    do {                                 \
-        if (!g_tally) MPO_LAUNCH_CHECK(); \
-    } while (0)
-
+// thread (mpo::Tally, MPO_TALLY_LAUNCH): no HIP call is made while a tally is set.
 struct Layer {
     int kind, stage, H, W, cin, cout, ks, coff;
     long long w_off = -1, g_off = -1, b_off = -1, mm_off = -1, mv_off = -1;   // params / state
@@ -1761,17 +1740,17 @@ int build_plan(DnPlan& p) {
 template <int KS, int NT>
 void launch_conv_t(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s) {
     auto kern = dn_conv_kernel<KS, NT>;
-    if (!g_tally)
+    if (!mpo::g_tally)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    DN_LAUNCH(kern, grid, dim3(256), lds, s, a);
+    MPO_TALLY_LAUNCH(kern, grid, dim3(256), lds, s, a);
 }
 
 template <int NT>
 void launch_wg3_t(const WgArgs& a, dim3 grid, size_t lds, hipStream_t s) {
     auto kern = dn_wgrad3_kernel<NT>;
-    if (!g_tally)
+    if (!mpo::g_tally)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    DN_LAUNCH(kern, grid, dim3(kWgWaves * 64), lds, s, a);
+    MPO_TALLY_LAUNCH(kern, grid, dim3(kWgWaves * 64), lds, s, a);
 }
 
 // dn_conv1x1_kernel: a 2 x 8 patch per wave (even H, W % 8 == 0), float4 channel
@@ -1784,8 +1763,8 @@ bool conv1x1_ok(const ConvArgs& a) {
 
 template <int NT, int CB>
 void launch_c1x1(const ConvArgs& a, dim3 grid, hipStream_t s) {
-    if (a.pool) DN_LAUNCH((dn_conv1x1_kernel<NT, CB, true>), grid, dim3(256), 0, s, a);
-    else DN_LAUNCH((dn_conv1x1_kernel<NT, CB, false>), grid, dim3(256), 0, s, a);
+    if (a.pool) MPO_TALLY_LAUNCH((dn_conv1x1_kernel<NT, CB, true>), grid, dim3(256), 0, s, a);
+    else MPO_TALLY_LAUNCH((dn_conv1x1_kernel<NT, CB, false>), grid, dim3(256), 0, s, a);
 }
 
 template <int NT>
@@ -1808,7 +1787,7 @@ int launch_conv1x1(const ConvArgs& a, int n_members, int B, hipStream_t s) {
         case 3: launch_c1x1_cb<3>(a, grid, cb, s); break;
         default: launch_c1x1_cb<4>(a, grid, cb, s); break;
     }
-    DN_LAUNCH_CHECK();
+    MPO_TALLY_LAUNCH_CHECK();
     return MPO_OK;
 }
 
@@ -1836,10 +1815,10 @@ int launch_conv(const ConvArgs& a, int n_members, int B, hipStream_t s) {
 template <int MT>
 void launch_wg1_mt(const WgArgs& a, dim3 grid, int nt, hipStream_t s) {
     switch (nt) {
-        case 1: DN_LAUNCH((dn_wgrad1_kernel<MT, 1>), grid, dim3(kWgWaves * 64), 0, s, a); break;
-        case 2: DN_LAUNCH((dn_wgrad1_kernel<MT, 2>), grid, dim3(kWgWaves * 64), 0, s, a); break;
-        case 3: DN_LAUNCH((dn_wgrad1_kernel<MT, 3>), grid, dim3(kWgWaves * 64), 0, s, a); break;
-        case 4: DN_LAUNCH((dn_wgrad1_kernel<MT, 4>), grid, dim3(kWgWaves * 64), 0, s, a); break;
+        case 1: MPO_TALLY_LAUNCH((dn_wgrad1_kernel<MT, 1>), grid, dim3(kWgWaves * 64), 0, s, a); break;
+        case 2: MPO_TALLY_LAUNCH((dn_wgrad1_kernel<MT, 2>), grid, dim3(kWgWaves * 64), 0, s, a); break;
+        case 3: MPO_TALLY_LAUNCH((dn_wgrad1_kernel<MT, 3>), grid, dim3(kWgWaves * 64), 0, s, a); break;
+        case 4: MPO_TALLY_LAUNCH((dn_wgrad1_kernel<MT, 4>), grid, dim3(kWgWaves * 64), 0, s, a); break;
         default: break;
     }
 }
@@ -1891,16 +1870,16 @@ int enqueue_prep(DnPlan& p, bool with_dgrad, hipStream_t s) {
         if (ly.kind == K_HEAD) continue;
         const int taps = ly.ks * ly.ks;
         const long long wms = (long long)ly.wf_rows * ly.wf_n16;
-        DN_LAUNCH(dn_prep_kernel, flat_grid(wms, p.na), dim3(256), 0, s, p.params, p.n_params, ly.w_off,
+        MPO_TALLY_LAUNCH(dn_prep_kernel, flat_grid(wms, p.na), dim3(256), 0, s, p.params, p.n_params, ly.w_off,
                   p.act + ly.wf_off, ((wms + 63) & ~63LL), taps, ly.cin, ly.cout, ly.wf_rows, ly.wf_n16, 0, p.mmap());
         if (with_dgrad && ly.kind != K_CONV0) {
             const long long dms = (long long)ly.wd_rows * ly.wd_n16;
-            DN_LAUNCH(dn_prep_kernel, flat_grid(dms, p.na), dim3(256), 0, s, p.params, p.n_params, ly.w_off,
+            MPO_TALLY_LAUNCH(dn_prep_kernel, flat_grid(dms, p.na), dim3(256), 0, s, p.params, p.n_params, ly.w_off,
                       p.act + ly.wd_off_act, ((dms + 63) & ~63LL), taps, ly.cin, ly.cout, ly.wd_rows,
                       ly.wd_n16, 1, p.mmap());
         }
     }
-    DN_LAUNCH_CHECK();
+    MPO_TALLY_LAUNCH_CHECK();
     return MPO_OK;
 }
 
@@ -1980,17 +1959,17 @@ int enqueue_forward(DnPlan& p, const float* x, const int* labels, const int* ord
         }
         if (train) {
             auto kern = bn_vec4(bn) ? dn_bn_stats_kernel<4> : dn_bn_stats_kernel<1>;
-            DN_LAUNCH(kern, dim3(ly.H, p.bn_S[li], n), dim3(256), 0, s, bn, bnp, p.bn_S[li], p.bn_bs[li]);
+            MPO_TALLY_LAUNCH(kern, dim3(ly.H, p.bn_S[li], n), dim3(256), 0, s, bn, bnp, p.bn_S[li], p.bn_bs[li]);
         }
-        DN_LAUNCH(dn_bn_coef_kernel, dim3(n), dim3(64), 0, s, bn, (const double*)bnp, p.bn_S[li]);
+        MPO_TALLY_LAUNCH(dn_bn_coef_kernel, dim3(n), dim3(64), 0, s, bn, (const double*)bnp, p.bn_S[li]);
         if (ly.kind == K_HEAD)   // the head's GAP reads z: the only site that stores it
-            DN_LAUNCH(dn_bn_apply_kernel, dim3(B * ly.H, n), dim3(256), 0, s, bn);
+            MPO_TALLY_LAUNCH(dn_bn_apply_kernel, dim3(B * ly.H, n), dim3(256), 0, s, bn);
         if (ly.kind == K_HEAD) {
             HeadArgs h = head_args(p, labels, order, ord_ms, row0, train);
             h.loss_out = loss_out; h.loss_sum = loss_sum; h.correct = correct;
             const size_t lds = (size_t)(h.C + h.classes) * sizeof(float);
-            DN_LAUNCH(dn_head_fwd_kernel, dim3(B, n), dim3(256), lds, s, h);
-            DN_LAUNCH(dn_head_reduce_kernel, dim3(n), dim3(256), 0, s, h, p.n_params);
+            MPO_TALLY_LAUNCH(dn_head_fwd_kernel, dim3(B, n), dim3(256), lds, s, h);
+            MPO_TALLY_LAUNCH(dn_head_reduce_kernel, dim3(n), dim3(256), 0, s, h, p.n_params);
             continue;
         }
         ConvArgs c{};
@@ -2016,12 +1995,12 @@ int enqueue_forward(DnPlan& p, const float* x, const int* labels, const int* ord
             DN_TRY(launch_conv<1>(c, n, B, s));
             const bool v4 = pool_vec4(ly.cout, p.sC[st + 1], tms, p.cat_ms[st + 1], p.act + ly.t_off,
                                       p.act + p.cat_off[st + 1]);
-            DN_LAUNCH(v4 ? dn_pool_fwd_kernel<4> : dn_pool_fwd_kernel<1>,
+            MPO_TALLY_LAUNCH(v4 ? dn_pool_fwd_kernel<4> : dn_pool_fwd_kernel<1>,
                       dim3((B * (ly.H / 2) + 1) / 2, n), dim3(256), 0, s, p.act + ly.t_off, tms,
                       p.act + p.cat_off[st + 1], p.cat_ms[st + 1], p.sC[st + 1], B, ly.H, ly.W, ly.cout, p.mmap());
         }
     }
-    DN_LAUNCH_CHECK();
+    MPO_TALLY_LAUNCH_CHECK();
     return MPO_OK;
 }
 
@@ -2030,11 +2009,11 @@ void enqueue_bn_bwd(DnPlan& p, const BnArgs& bn, int li, hipStream_t s, int fuse
     const int S = fused_S > 0 ? fused_S : p.bn_S[li];
     const bool v4 = bn_vec4(bn);
     if (fused_S <= 0)   // else the input-gradient conv's epilogue wrote the slice partials
-        DN_LAUNCH(v4 ? dn_bn_bwd_reduce_kernel<4> : dn_bn_bwd_reduce_kernel<1>, dim3(bn.H, S, p.na),
+        MPO_TALLY_LAUNCH(v4 ? dn_bn_bwd_reduce_kernel<4> : dn_bn_bwd_reduce_kernel<1>, dim3(bn.H, S, p.na),
                   dim3(256), 0, s, bn, bnp, S, p.bn_bs[li]);
-    if (fused_S > 0) DN_LAUNCH(dn_bn_bwd_fold_wide_kernel, dim3(bn.H, p.na), dim3(64), 0, s, bn, bnp, S);
-    else DN_LAUNCH(dn_bn_bwd_fold_kernel, dim3(p.na), dim3(64), 0, s, bn, bnp, S);
-    DN_LAUNCH(v4 ? dn_bn_bwd_apply_kernel<4> : dn_bn_bwd_apply_kernel<1>, dim3((p.B * bn.H + 1) / 2, p.na),
+    if (fused_S > 0) MPO_TALLY_LAUNCH(dn_bn_bwd_fold_wide_kernel, dim3(bn.H, p.na), dim3(64), 0, s, bn, bnp, S);
+    else MPO_TALLY_LAUNCH(dn_bn_bwd_fold_kernel, dim3(p.na), dim3(64), 0, s, bn, bnp, S);
+    MPO_TALLY_LAUNCH(v4 ? dn_bn_bwd_apply_kernel<4> : dn_bn_bwd_apply_kernel<1>, dim3((p.B * bn.H + 1) / 2, p.na),
               dim3(256), 0, s, bn, (const double*)bnp, S);
 }
 
@@ -2047,7 +2026,7 @@ int enqueue_backward(DnPlan& p, const float* x, const int* order, long long ord_
     // backward); the slabs and the gradient slots are s2's alone.  The transition dOut
     // buffer dt is shared by the transitions, so s waits for s2 before each pool
     // backward refills it; s waits for everything at the end (Adam reads the gradients).
-    hipStream_t s2 = g_tally ? nullptr : p.side.get(s);   // a tally never touches HIP
+    hipStream_t s2 = mpo::g_tally ? nullptr : p.side.get(s);   // a tally never touches HIP
     p.side2.slot = 1;
     hipStream_t s3 = s2 && p.wg2 ? p.side2.get(s) : nullptr;
     p.side3.slot = 2;
@@ -2082,7 +2061,7 @@ int enqueue_backward(DnPlan& p, const float* x, const int* order, long long ord_
             if (s4) MPO_HIP(p.side3.join(s, s4));
             const bool v4 = pool_vec4(ly.cout, p.sC[st + 1], p.dt_ms, p.cat_ms[st + 1], p.act + p.dt_off,
                                       p.act + p.dcat_off[st + 1]);
-            DN_LAUNCH(v4 ? dn_pool_bwd_kernel<4> : dn_pool_bwd_kernel<1>, dim3((B * ly.H + 1) / 2, n),
+            MPO_TALLY_LAUNCH(v4 ? dn_pool_bwd_kernel<4> : dn_pool_bwd_kernel<1>, dim3((B * ly.H + 1) / 2, n),
                       dim3(256), 0, s, p.act + p.dcat_off[st + 1],
                       p.cat_ms[st + 1], p.sC[st + 1], p.act + p.dt_off, p.dt_ms, B, ly.H, ly.W, ly.cout, p.mmap());
             dout = p.act + p.dt_off; dout_ms = p.dt_ms; dout_ps = ly.cout;
@@ -2111,7 +2090,7 @@ int enqueue_backward(DnPlan& p, const float* x, const int* order, long long ord_
         }
         DN_TRY(launch_wgrad(w, ly.ks, n, ly.G, sw));
         const long long cnt = (long long)ly.ks * ly.ks * ly.cin * ly.cout;
-        DN_LAUNCH(dn_wgrad_reduce_kernel, flat_grid(cnt, n), dim3(256), 0, sw, (const float*)w.part,
+        MPO_TALLY_LAUNCH(dn_wgrad_reduce_kernel, flat_grid(cnt, n), dim3(256), 0, sw, (const float*)w.part,
                   w.part_ms, ly.G, cnt, p.grads, p.n_params, ly.w_off, p.mmap());
         if (ly.kind == K_CONV0) continue;
         // input gradient: 'same' conv of dOut with the rotated, transposed kernel -> dz
@@ -2139,7 +2118,7 @@ int enqueue_backward(DnPlan& p, const float* x, const int* order, long long ord_
     if (s2) MPO_HIP(p.side.join(s, s2));
     if (s3) MPO_HIP(p.side2.join(s, s3));
     if (s4) MPO_HIP(p.side3.join(s, s4));
-    DN_LAUNCH_CHECK();
+    MPO_TALLY_LAUNCH_CHECK();
     return MPO_OK;
 }
 
@@ -2150,9 +2129,9 @@ int enqueue_train(DnPlan& p, const float* x, const int* labels, const int* order
     DN_TRY(enqueue_prep(p, true, s));
     DN_TRY(enqueue_forward(p, x, labels, order, ord_ms, row0, true, loss_out, nullptr, nullptr, s));
     DN_TRY(enqueue_backward(p, x, order, ord_ms, row0, s));
-    DN_LAUNCH(dn_adam_kernel, flat_grid(p.n_params, p.na), dim3(256), 0, s, p.params, p.grads, p.m, p.v, p.n_params,
+    MPO_TALLY_LAUNCH(dn_adam_kernel, flat_grid(p.n_params, p.na), dim3(256), 0, s, p.params, p.grads, p.m, p.v, p.n_params,
               p.n_params, (const float*)(p.act + p.lr_off), step + 1, p.mmap());
-    DN_LAUNCH_CHECK();
+    MPO_TALLY_LAUNCH_CHECK();
     return MPO_OK;
 }
 
@@ -2292,10 +2271,10 @@ int mpo_dn_step_work(const void* handle, int64_t* workgroups, int64_t* launches)
     alignas(256) static float stand_in[64];
     float* const saved[6] = {p.params, p.grads, p.m, p.v, p.state, p.act};
     if (!p.bound) p.params = p.grads = p.m = p.v = p.state = p.act = stand_in;
-    Tally t;
-    g_tally = &t;
+    mpo::Tally t;
+    mpo::g_tally = &t;
     const int rc = enqueue_train(p, stand_in, nullptr, reinterpret_cast<const int*>(stand_in), p.B, 0, 0, stand_in, nullptr);
-    g_tally = nullptr;
+    mpo::g_tally = nullptr;
     p.params = saved[0]; p.grads = saved[1]; p.m = saved[2]; p.v = saved[3]; p.state = saved[4]; p.act = saved[5];
     if (rc != MPO_OK) return rc;
     *workgroups = t.workgroups;
@@ -2324,7 +2303,7 @@ int mpo_dn_penalty(void* handle, float* out, void* stream) {
     MPO_CHECK_ARG(handle && out, "mpo_dn_penalty: null pointer");
     DnPlan& p = *static_cast<DnPlan*>(handle);
     MPO_CHECK_ARG(p.bound, "mpo_dn_penalty: plan not bound");
-    DN_LAUNCH(dn_penalty_kernel, dim3(p.n), dim3(256), 0, static_cast<hipStream_t>(stream), p.params,
+    MPO_TALLY_LAUNCH(dn_penalty_kernel, dim3(p.n), dim3(256), 0, static_cast<hipStream_t>(stream), p.params,
               p.n_params, p.n_params, out);
     MPO_LAUNCH_CHECK();
     return MPO_OK;

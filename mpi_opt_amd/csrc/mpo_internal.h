@@ -119,6 +119,7 @@ struct SideStream {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     int device = -1;
     SideStream() = default;
+    explicit SideStream(int slot_) : slot(slot_) {}
     SideStream(const SideStream&) = delete;
     SideStream& operator=(const SideStream&) = delete;
     ~SideStream() { release(); }
@@ -165,6 +166,18 @@ struct SideStream {
         return hipStreamWaitEvent(s, ev_join, 0);
     }
 };
+
+// The population engines' mpo_*_step_work walk the enqueue code of a train step with a
+// tally set on their thread: every MPO_TALLY_LAUNCH adds its grid to the tally instead of
+// running, so the figures cannot drift from what a step launches.  No HIP call is made
+// while a tally is set: code on the walked path guards its other HIP calls with g_tally.
+struct Tally {
+    long long workgroups = 0, launches = 0;
+};
+inline thread_local Tally* g_tally = nullptr;
+
+// hipGetLastError() after a launch that a tally may have counted instead
+inline hipError_t tally_launch_error() { return g_tally ? hipSuccess : hipGetLastError(); }
 
 // Static (compile-time) LDS bytes of a kernel, from its code object.
 inline size_t static_lds_bytes(const void* kern) {
@@ -245,6 +258,22 @@ hipError_t argmin_fold(const double* part_val, const long long* part_idx, int n_
     } while (0)
 
 #define MPO_LAUNCH_CHECK() MPO_HIP(hipGetLastError())
+
+// A kernel launch / launch check on a path that mpo_*_step_work walks (mpo::Tally)
+#define MPO_TALLY_LAUNCH(kern, grid, block, lds, stream, ...)                    \
+    do {                                                                         \
+        if (::mpo::g_tally) {                                                    \
+            const dim3 g_ = (grid);                                              \
+            ::mpo::g_tally->workgroups += (long long)g_.x * g_.y * g_.z;         \
+            ++::mpo::g_tally->launches;                                          \
+        } else {                                                                 \
+            hipLaunchKernelGGL(kern, grid, block, lds, stream, __VA_ARGS__);     \
+        }                                                                        \
+    } while (0)
+#define MPO_TALLY_LAUNCH_CHECK()                    \
+    do {                                            \
+        if (!::mpo::g_tally) MPO_LAUNCH_CHECK();    \
+    } while (0)
 
 #define MPO_GUARD_BEGIN try {
 #define MPO_GUARD_END                                         \

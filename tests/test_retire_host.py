@@ -80,6 +80,60 @@ def test_mnist_all_retired_then_all_back():
     L.mpo_pop_destroy(h)
 
 
+def plan_env(monkeypatch, env):
+    """The plan knobs are read when a plan is created."""
+    monkeypatch.delenv("MPO_POP_PLAN", raising=False)
+    monkeypatch.delenv("MPO_POP_PROFILE", raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
+def masked_work(members, retired):
+    L = _lib.lib()
+    h = pop_create(members)
+    _lib.check(L.mpo_pop_set_active(h, mask_bytes(len(members), retired), None), "mpo_pop_set_active")
+    out = work(L.mpo_pop_step_work, h)
+    L.mpo_pop_destroy(h)
+    return out
+
+
+@pytest.mark.parametrize("serial", [{"MPO_POP_PLAN": "streams=1"}, {"MPO_POP_PROFILE": "1"}], ids=["streams1", "profile"])
+@pytest.mark.parametrize("retired", [[], [2], [0, 2, 5], [1, 2, 3, 4, 5]])
+def test_mnist_serial_step_is_the_same_items_in_one_launch_fewer(monkeypatch, serial, retired):
+    """A step on one stream (streams=1, or profiled) reduces both halves of the weight-gradient
+    slabs in one launch of twice the grid; with the side stream they are two launches.  The
+    walk of mpo_pop_step_work takes the form the real step takes, from the plan alone."""
+    plan_env(monkeypatch, {})
+    forked = masked_work(MEMBERS, retired)
+    plan_env(monkeypatch, serial)
+    one_stream = masked_work(MEMBERS, retired)
+    assert one_stream[0] == forked[0] > 0
+    assert one_stream[1] == forked[1] - 1
+
+
+def test_mnist_step_work_before_bind_touches_no_device(monkeypatch):
+    """mpo_pop_step_work walks the step's own enqueue code under a tally: before bind, with no
+    device, it reports what the hand-written count reported (the figures of the parent of the
+    tally's introduction for MEMBERS at batch 10) and makes no HIP call -- a launch would fail
+    here without a GPU, and an event of the phase timer that cannot be created turns the timer
+    off, which mpo_pop_profile would report as MPO_ENOTSUP."""
+    L = _lib.lib()
+    for env, full, part in [({}, (2596, 41), (1525, 26)),
+                            ({"MPO_POP_PLAN": "streams=1"}, (2596, 40), (1525, 25)),
+                            ({"MPO_POP_PROFILE": "1"}, (2596, 40), (1525, 25))]:
+        plan_env(monkeypatch, env)
+        h = pop_create(MEMBERS)
+        assert work(L.mpo_pop_step_work, h) == full
+        assert work(L.mpo_pop_step_work, h) == full              # a walk leaves the plan as it found it
+        _lib.check(L.mpo_pop_set_active(h, mask_bytes(len(MEMBERS), [0, 2, 5]), None), "mpo_pop_set_active")
+        assert work(L.mpo_pop_step_work, h) == part
+        buf = ctypes.create_string_buffer(256)
+        rc = L.mpo_pop_profile(h, buf, len(buf), 0)
+        assert buf.value == b""                                  # no phase was ever marked
+        assert rc == (0 if "MPO_POP_PROFILE" in env else 3)      # MPO_OK: the timer is still on / MPO_ENOTSUP
+        L.mpo_pop_destroy(h)
+
+
 def dn_create(n, arch=(16, 16, 3, 10, 7, 3, 12, 16), batch=8):
     h = ctypes.c_void_p()
     a = _lib.MpoDnArch(*arch)
