@@ -309,6 +309,86 @@ int mpo_gp_acq_ps_grad_host(const MpoGpModel* fmodel, const MpoGpModel* tmodel, 
                             double* parts_host, void* stream);
 
 /* ------------------------------------------------------------------------
+ * A committee of exact GPs as one surrogate: the robust Bayesian committee machine (rBCM;
+ * Deisenroth & Ng, "Distributed Gaussian Processes", ICML 2015).  NOT the reference's
+ * semantics (skopt fits one GP to all told points); it serves the opt-in
+ * Optimizer(surrogate="committee") past one GP's 2048 observations.  `models` is a HOST array
+ * of E prepared MpoGpModel ("experts") over disjoint parts of the observations that share d,
+ * dp, amp, the length scales and ONE target normalisation (y_mean, y_std).  In normalised
+ * units expert e gives the mean m_e and the variance v_e = amp - q_e at a point; with
+ *   r_e = v_e / amp clamped to [2^-52, 1]   (a clamped r_e has zero derivative; r_e = 1
+ *                                            contributes nothing)
+ *   b_e = -ln(r_e) / 2
+ *   S   = sum_e b_e (1 / r_e - 1)           P = 1 + S >= 1: never less certain than the prior
+ *   M   = sum_e b_e m_e / r_e
+ * the committee's posterior is mu = y_mean + y_std M / P, sd = y_std sqrt(amp / P); EI, PI
+ * and LCB and their gradients are mpo_gp_acq_score's / mpo_gp_acq_grad's on (mu, sd).  Both
+ * sums start from 0 and add expert 0 .. E-1 in that order: a point's outputs are the same
+ * bits whatever m, the batch or the launch.  E = 1 is the rBCM of one expert (b_0 != 1), not
+ * that expert's own posterior.
+ * Refused on the host before any launch, with a message in mpo_last_error(): MPO_EINVAL for
+ * E outside [1, MPO_COMMITTEE_MAX], a null or malformed expert, experts that differ in d,
+ * dp, amp, y_mean or y_std; MPO_ENOTSUP for an expert with n > 2048.  The length scales are
+ * device data: mpo_gp_committee_check compares them (and synchronises); the other entry
+ * points only enqueue and take them on trust.  A caller who skips the check and passes experts
+ * with different length scales gets NO error: every expert is then scored and differentiated
+ * under its own length scales, which is a different model from the one documented here.
+ * ---------------------------------------------------------------------- */
+#define MPO_COMMITTEE_MAX 32
+
+/* The refusals above, then the experts' length scales read back and compared (MPO_EINVAL
+ * when two differ).  Synchronises `stream`; call it once after the experts are prepared. */
+int mpo_gp_committee_check(const MpoGpModel* models, int E, void* stream);
+
+/* Workspace bytes of mpo_gp_committee_score: the largest expert's scoring workspace (the
+ * passes run one after the other), 4 rows of m doubles (the running S and M, one expert's
+ * mu and sd) and the finish pass's top-k lists -- independent of E.  0 for what that call
+ * refuses. */
+size_t mpo_gp_committee_ws_bytes(const MpoGpModel* models, int E, int64_t m, int k);
+
+/* Score m candidates ([m][d] device) under the committee: each expert's own scoring path
+ * (resident or streamed, as mpo_gp_score_path says) writes its (mu, sd) rows, one elementwise
+ * pass folds them into S and M, and the last expert's pass also finishes:
+ *   mu, sd                 the committee's posterior mean / std          ([m] or NULL)
+ *   vals[a*m + i]          the minimised value of acquisition a in {EI, PI, LCB} order (rows
+ *                          of unset flags untouched)                      ([3][m] or NULL)
+ *   topk_idx/val[a*k + r]  the k smallest values of acquisition a by (value, index): lowest
+ *                          index on ties; index -1 where m < k (NULL with k = 0)
+ * MPO_EINVAL also for m < 1, bad flags, k outside [0, MPO_TOPK_MAX], k > 0 without top-k
+ * outputs, k = 0 with none of mu, sd, vals, a workspace smaller than
+ * mpo_gp_committee_ws_bytes.  Only enqueues work: no allocation, no host synchronisation,
+ * no atomics, capturable in a graph.  The experts' length scales are NOT compared here
+ * (mpo_gp_committee_check does that once): see above for what unequal ones give. */
+int mpo_gp_committee_score(const MpoGpModel* models, int E, const double* cand, int64_t m,
+                           double y_opt, double xi, double kappa, unsigned flags,
+                           double* mu, double* sd, double* vals, int k,
+                           int64_t* topk_idx, double* topk_val,
+                           void* ws, size_t ws_bytes, void* stream);
+
+/* The polish objective under the committee: f[b] and g[b][d] of acquisition acq[b] (device
+ * int32, MPO_ACQ_EI / MPO_ACQ_PI / MPO_ACQ_LCB) at the points x [batch][d] (device).  One
+ * launch, one workgroup per point: every expert's posterior and gradient one after the other
+ * in the same LDS, each by the sequence of mpo_gp_acq_grad's kernel, the wave form (16 or 4,
+ * mpo_gp_committee_grad_path) chosen for the largest expert.  Every sum runs in a fixed order:
+ * a point's f and g are the same bits whatever the batch or its order.  batch in [1, 65535].
+ * The experts' length scales are NOT compared here (mpo_gp_committee_check): each expert's
+ * posterior is taken under its own, as mpo_gp_committee_score takes it. */
+int mpo_gp_committee_grad(const MpoGpModel* models, int E, const double* x, int batch,
+                          const int32_t* acq, double y_opt, double xi, double kappa,
+                          double* f, double* g, void* stream);
+
+/* Waves per point (16 or 4) of the kernel mpo_gp_committee_grad launches, or negative
+ * (-MPO_EINVAL, -MPO_ENOTSUP) when it would be refused.  Needs a device, as
+ * mpo_gp_acq_grad_path does. */
+int mpo_gp_committee_grad_path(const MpoGpModel* models, int E);
+
+/* One polish round from the host: mpo_gp_committee_grad with x, acq, f, g in pinned host
+ * memory, read and written in place, then one synchronisation of `stream`. */
+int mpo_gp_committee_grad_host(const MpoGpModel* models, int E, const double* x_host, int batch,
+                               const int32_t* acq_host, double y_opt, double xi, double kappa,
+                               double* f_host, double* g_host, void* stream);
+
+/* ------------------------------------------------------------------------
  * The JOINT posterior of a prepared model over m query points (transformed space,
  * [m][d] device): what sklearn's GaussianProcessRegressor.predict(X, return_cov=True)
  * and sample_y(X, n_samples) give (_gpr.py:370-470, 472-507), for skopt's fitted GP
@@ -653,6 +733,16 @@ int mpo_gp_polish_ps_host(const MpoGpModel* fmodel, const MpoGpModel* tmodel, co
                           const int32_t* acq, int nruns, const double* bounds, const MpoLbfgsbOptions* opts,
                           double y_opt, double xi, double* x_host, int32_t* acq_host, double* f_host, double* g_host,
                           double* x_out, double* f_out, int32_t* stats, int32_t* rounds, void* stream);
+
+/* mpo_gp_polish_host on a committee's objective (NOT the reference's semantics): L-BFGS-B
+ * from starts [nruns][d] on acquisition acq[r] under the E experts' rBCM posterior, one
+ * mpo_gp_committee_grad_host round per iteration of all live runs through the same pinned
+ * buffers. */
+int mpo_gp_polish_committee_host(const MpoGpModel* models, int E, const double* starts, const int32_t* acq,
+                                 int nruns, const double* bounds, const MpoLbfgsbOptions* opts, double y_opt,
+                                 double xi, double kappa, double* x_host, int32_t* acq_host, double* f_host,
+                                 double* g_host, double* x_out, double* f_out, int32_t* stats, int32_t* rounds,
+                                 void* stream);
 
 /* Each draw of a set of sample paths minimised from its own start (NOT the reference's
  * semantics): L-BFGS-B from starts [nruns][d] on draw[r] of `paths` (mpo_gp_paths_grad_host

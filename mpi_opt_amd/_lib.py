@@ -17,6 +17,7 @@ MPO_ACQ_EI = 1
 MPO_ACQ_PI = 2
 MPO_ACQ_LCB = 4
 MPO_TOPK_MAX = 8
+MPO_COMMITTEE_MAX = 32
 MPO_JOINT_MAX = 4096
 MPO_JOINT_SMAX = 1048560
 MPO_PD_GMAX = 64
@@ -141,6 +142,12 @@ SIGNATURES = {
     "mpo_gp_acq_ps_grad_path": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpModel)]),
     "mpo_gp_acq_ps_grad_host": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpModel), _P, _I, _P, _D, _D, _P,
                                      _P, _P, _P]),
+    "mpo_gp_committee_check": (_I, [_P, _I, _P]),
+    "mpo_gp_committee_ws_bytes": (_SZ, [_P, _I, _I64, _I]),
+    "mpo_gp_committee_score": (_I, [_P, _I, _P, _I64, _D, _D, _D, _U, _P, _P, _P, _I, _P, _P, _P, _SZ, _P]),
+    "mpo_gp_committee_grad": (_I, [_P, _I, _P, _I, _P, _D, _D, _D, _P, _P, _P]),
+    "mpo_gp_committee_grad_path": (_I, [_P, _I]),
+    "mpo_gp_committee_grad_host": (_I, [_P, _I, _P, _I, _P, _D, _D, _D, _P, _P, _P]),
     "mpo_gp_joint_ws_bytes": (_SZ, [ctypes.POINTER(MpoGpModel), _I, _I]),
     "mpo_gp_posterior_cov": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _P, _I, _P, _SZ, _P]),
     "mpo_gp_sample": (_I, [ctypes.POINTER(MpoGpModel), _P, _I, _P, _I, _D, _P, _P, _P, _P, _SZ, _P]),
@@ -166,6 +173,8 @@ SIGNATURES = {
                                 _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mpo_gp_polish_ps_host": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpModel), _P, _P, _I, _P,
                                    ctypes.POINTER(MpoLbfgsbOptions), _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mpo_gp_polish_committee_host": (_I, [_P, _I, _P, _P, _I, _P, ctypes.POINTER(MpoLbfgsbOptions), _D, _D, _D, _P, _P,
+                                          _P, _P, _P, _P, _P, _P, _P]),
     "mpo_gp_paths_polish_host": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpPaths), _P, _P, _I, _P,
                                       ctypes.POINTER(MpoLbfgsbOptions), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mpo_pop_create": (_I, [ctypes.POINTER(MpoCnnSpec), _I, _I, ctypes.POINTER(ctypes.c_void_p)]),

@@ -28,7 +28,12 @@ _FTOL, _GTOL, _MAXITER, _MAXFUN = 2.220446049250313e-09, 1e-5, 15000, 15000
 
 
 def _objective_model(model):
-    """The objective's surrogate of a fitted model: a cost-aware pair reports ``estimators_[0]``."""
+    """The objective's surrogate of a fitted model: a cost-aware pair reports ``estimators_[0]``.
+    A committee of experts (``Optimizer(surrogate="committee")``) is refused: the report's
+    kernels read one exact GP."""
+    if getattr(model, "surrogate", None) == "committee":
+        raise ValueError('the objective report, partial_dependence and expected_minimum do not take the "committee" '
+                         "surrogate: they read one exact GP, a committee holds several experts")
     return model.estimators_[0] if hasattr(model, "estimators_") else model
 
 

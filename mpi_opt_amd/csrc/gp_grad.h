@@ -39,7 +39,11 @@ inline GradModel grad_model(const MpoGpModel& m) {
 // caller's static LDS.  Every sum runs in a fixed order given (NW, n, d).
 // Threads j < d leave with mu, sd and their component of grad mu, grad sd.  Ends behind a
 // barrier: the LDS is free for the next model.
-template <int NW>
+// TAIL_UNROLL > 0 bounds the unroll of the last sum over the NW * 2 groups (the same additions in
+// the same order): a caller that runs this routine inside a loop of runtime length
+// (gp_committee.hip) has less register room than straight-line code; 0 leaves the loop to the
+// compiler, as the callers that name no value get it.
+template <int NW, int TAIL_UNROLL = 0>
 __device__ __forceinline__ void posterior_grad(const GradModel& gm, int n, int d, const double* __restrict__ x,
                                                double* sm, double* xp, double* red, double (*ga)[32],
                                                double (*gu)[32], double& mu, double& sd, double& mu_g, double& sd_g) {
@@ -138,9 +142,17 @@ __device__ __forceinline__ void posterior_grad(const GradModel& gm, int n, int d
     if (tid < d) {
         const int j = tid;
         double sa = 0.0, su = 0.0;
-        for (int grp = 0; grp < kGroups; ++grp) {
-            sa += ga[grp][j];
-            su += gu[grp][j];
+        if constexpr (TAIL_UNROLL > 0) {
+#pragma unroll TAIL_UNROLL
+            for (int grp = 0; grp < kGroups; ++grp) {
+                sa += ga[grp][j];
+                su += gu[grp][j];
+            }
+        } else {
+            for (int grp = 0; grp < kGroups; ++grp) {
+                sa += ga[grp][j];
+                su += gu[grp][j];
+            }
         }
         const double inv_ls = 1.0 / gm.ls[j];
         double var = amp - q;

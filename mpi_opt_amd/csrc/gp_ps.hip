@@ -16,6 +16,7 @@
 //                       one launch, one workgroup per point
 
 #include "gp_grad.h"
+#include "gp_topk.h"
 
 #include <algorithm>
 
@@ -26,7 +27,7 @@ using mpo::grad_model;
 using mpo::GradModel;
 using mpo::lex_less;
 using mpo::posterior_grad;
-using mpo::wave_lex_min;
+using mpo::WaveTopk;
 
 constexpr unsigned kPsFlags = MPO_ACQ_EI | MPO_ACQ_PI;
 
@@ -38,47 +39,6 @@ __device__ __forceinline__ double inv_time(double mu, double s) { return exp(fma
 // workgroup, one candidate per lane and step, at most 4 workgroups for each of the 256 CUs.
 constexpr int kFinThreads = 256;
 constexpr int kFinGridCap = 1024;
-
-// One wave's running top-k of (value, index), the same list in every lane.
-struct WaveTopk {
-    double v[MPO_TOPK_MAX];
-    long long i[MPO_TOPK_MAX];
-    double thr_v;     // entry k - 1: what a candidate has to beat
-    long long thr_i;
-    __device__ __forceinline__ void init() {
-#pragma unroll
-        for (int r = 0; r < MPO_TOPK_MAX; ++r) { v[r] = __builtin_huge_val(); i[r] = 0x7fffffffffffffffLL; }
-        thr_v = v[0];
-        thr_i = i[0];
-    }
-    // the lanes' candidates (cv, ci) of one step; at most k of them enter
-    __device__ __forceinline__ void offer(double cv, long long ci, int k) {
-        while (__ballot(lex_less(cv, ci, thr_v, thr_i))) {
-            double bv = cv;
-            long long bi = ci;
-            wave_lex_min(bv, bi);
-            if (ci == bi) { cv = __builtin_huge_val(); ci = 0x7fffffffffffffffLL; }
-#pragma unroll
-            for (int s = 0; s < MPO_TOPK_MAX; ++s) {
-                if (s < k && lex_less(bv, bi, v[s], i[s])) {
-                    const double tv = v[s];
-                    const long long ti = i[s];
-                    v[s] = bv; i[s] = bi; bv = tv; bi = ti;
-                }
-            }
-#pragma unroll
-            for (int s = 0; s < MPO_TOPK_MAX; ++s) {
-                if (s == k - 1) { thr_v = v[s]; thr_i = i[s]; }
-            }
-        }
-    }
-    __device__ __forceinline__ void store(long long* __restrict__ pi, double* __restrict__ pv, size_t off, int k) const {
-#pragma unroll
-        for (int r = 0; r < MPO_TOPK_MAX; ++r) {
-            if (r < k) { pv[off + r] = v[r]; pi[off + r] = i[r]; }
-        }
-    }
-};
 
 // a [2][m] (rows EI, PI of fmodel's scoring pass; rows of unset flags are not read), mu / sd
 // [m] of tmodel's.  vals [2][m], inv_t [m]: optional.  part_idx / part_val: [waves][3][k],

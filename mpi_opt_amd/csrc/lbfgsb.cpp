@@ -1348,6 +1348,24 @@ int mpo_gp_polish_ps_host(const MpoGpModel* fmodel, const MpoGpModel* tmodel, co
     MPO_GUARD_END
 }
 
+int mpo_gp_polish_committee_host(const MpoGpModel* models, int E, const double* starts, const int32_t* acq,
+                                 int nruns, const double* bounds, const MpoLbfgsbOptions* opts, double y_opt,
+                                 double xi, double kappa, double* x_host, int32_t* acq_host, double* f_host,
+                                 double* g_host, double* x_out, double* f_out, int32_t* stats, int32_t* rounds,
+                                 void* stream) {
+    MPO_GUARD_BEGIN
+    if (const int rc = mpo::committee_models_ok("mpo_gp_polish_committee_host", models, E)) return rc;
+    MPO_CHECK_ARG(acq && x_host && acq_host && f_host && g_host && x_out && f_out,
+                  "mpo_gp_polish_committee_host: null pointer");
+    MPO_CHECK_ARG(options_ok(models[0].d, nruns, starts, bounds, opts),
+                  "mpo_gp_polish_committee_host: bad options / bounds");
+    return polish_drive(models[0].d, nruns, starts, bounds, opts, acq, x_host, acq_host, f_host, g_host, x_out,
+                        f_out, stats, rounds, [&](int b) {
+        return mpo_gp_committee_grad_host(models, E, x_host, b, acq_host, y_opt, xi, kappa, f_host, g_host, stream);
+    });
+    MPO_GUARD_END
+}
+
 int mpo_gp_paths_polish_host(const MpoGpModel* model, const MpoGpPaths* paths, const double* starts,
                              const int32_t* draw, int nruns, const double* bounds, const MpoLbfgsbOptions* opts,
                              double* x_host, int32_t* draw_host, double* f_host, double* g_host, double* x_out,

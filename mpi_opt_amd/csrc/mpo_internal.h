@@ -230,6 +230,11 @@ constexpr int kTopkMergeGroups = 256;
 hipError_t topk_merge(const long long* part_idx, const double* part_val, int nparts, int k, unsigned flags,
                       long long* mid_idx, double* mid_val, long long* out_idx, double* out_val, hipStream_t s);
 
+// The host-side refusals shared by every mpo_gp_committee_* entry point (gp_committee.hip) and
+// mpo_gp_polish_committee_host (lbfgsb.cpp): MPO_OK, or MPO_EINVAL / MPO_ENOTSUP with the message
+// set under `who` (null: a silent query).  Reads the host structs only.
+int committee_models_ok(const char* who, const MpoGpModel* models, int E);
+
 // The samplers' argmin fold (gp_paths.hip: argmin_fold_kernel; gp_joint.hip folds with it
 // too): argmin[r] / minval[r] (either may be null) of draw r < n_draws from its nb
 // workgroup partials part_val / part_idx [r * nb + b], folded in order, ties to the lowest

@@ -39,7 +39,9 @@ class DeviceGP:
     (WhiteKernel; used in the factorisation, zeroed for prediction as skopt does).
     """
 
-    def __init__(self, X, y, amp, length_scale, noise, device=None):
+    def __init__(self, X, y, amp, length_scale, noise, device=None, norm=None):
+        """``norm`` = ``(y_mean, y_std)``: an explicit target normalisation instead of this
+        data's own (an expert of a committee takes the one of all told values)."""
         self.device = _dev(device)
         X = np.ascontiguousarray(np.asarray(X, dtype=np.float64))
         y = np.asarray(y, dtype=np.float64).reshape(-1)
@@ -47,7 +49,11 @@ class DeviceGP:
             raise ValueError(f"bad GP data shapes X={X.shape} y={y.shape}")
         n, d = X.shape
         ls = np.broadcast_to(np.asarray(length_scale, dtype=np.float64), (d,)).copy()
-        y_mean, y_std, y_norm = _normalise(y)
+        if norm is None:
+            y_mean, y_std, y_norm = _normalise(y)
+        else:
+            y_mean, y_std = float(norm[0]), float(norm[1])
+            y_norm = (y - y_mean) / y_std
         self.n, self.d = n, d
         self.amp, self.noise = float(amp), float(noise)
         self.length_scale = ls
@@ -500,6 +506,98 @@ def polish_ps(fgp, tgp, starts, acq_codes, y_opt, xi, bounds, ftol, maxiter=20, 
     x, f, _, _ = _run_polish("mpo_gp_polish_ps_host", (ctypes.byref(fgp.model), ctypes.byref(tgp.model)),
                              (float(y_opt), float(xi)), starts, acq_codes, bounds, ftol, maxiter, gtol, maxfun,
                              fgp._ensure_ag(len(starts)), fgp._ag_stream)
+    return [(x[r], float(f[r])) for r in range(len(starts))]
+
+
+# -- a committee of experts (rBCM): E models over disjoint parts of the observations ----------
+class DeviceCommittee:
+    """The host array of E prepared experts (:class:`DeviceGP`, built with one shared
+    ``norm``, amp and length scales) that the ``mpo_gp_committee_*`` entry points take, with
+    the committee's workspace and pinned round buffers.  ``mpo_gp_committee_check`` runs
+    once here: the shared fields and the length scales are compared."""
+
+    def __init__(self, experts):
+        experts = list(experts)
+        if not 1 <= len(experts) <= _lib.MPO_COMMITTEE_MAX:
+            raise ValueError(f"a committee holds 1 .. {_lib.MPO_COMMITTEE_MAX} experts, got {len(experts)}")
+        if len({e.device for e in experts}) != 1:
+            raise ValueError("the experts of a committee must share one device")
+        self.experts = experts
+        self.E = len(experts)
+        self.device, self.d = experts[0].device, experts[0].d
+        self.models = (_lib.MpoGpModel * self.E)()
+        for i, e in enumerate(experts):
+            ctypes.memmove(ctypes.byref(self.models[i]), ctypes.byref(e.model), ctypes.sizeof(_lib.MpoGpModel))
+        self._ws = None
+        with torch.cuda.device(self.device):
+            check(lib().mpo_gp_committee_check(self.models, self.E, _lib.stream_handle(self.device)),
+                  "mpo_gp_committee_check")
+
+    as_candidates = DeviceGP.as_candidates
+    _ensure_ag = DeviceGP._ensure_ag
+
+    @property
+    def grad_path(self):
+        """``mpo_gp_committee_grad_path``: waves per point (16 or 4) of the polish kernel."""
+        with torch.cuda.device(self.device):
+            return int(lib().mpo_gp_committee_grad_path(self.models, self.E))
+
+
+def score_committee(com, cand, y_opt, acqs=("EI",), xi=0.01, kappa=1.96, k=0, want_mu_sd=True, want_values=True):
+    """``mpo_gp_committee_score``: :meth:`DeviceGP.score` under the rBCM posterior of the
+    :class:`DeviceCommittee` ``com`` (NOT the reference's semantics).  Returns the same dict of
+    device tensors: ``mu``, ``sd`` (m,), ``values`` {acq: (m,)}, ``topk`` {acq: (idx, val)}."""
+    c = com.as_candidates(cand)
+    m = c.shape[0]
+    flags = 0
+    for a in acqs:
+        flags |= _lib.ACQ_FLAGS[a]
+    L = lib()
+    need = L.mpo_gp_committee_ws_bytes(com.models, com.E, m, int(k))
+    if need == 0:
+        raise _lib.MpoError("mpo_gp_committee_ws_bytes rejected the shape")
+    if com._ws is None or com._ws.numel() < need:
+        com._ws = torch.empty(need, dtype=torch.uint8, device=com.device)
+    dev = com.device
+    mu = torch.empty(m, dtype=torch.float64, device=dev) if want_mu_sd else None
+    sd = torch.empty(m, dtype=torch.float64, device=dev) if want_mu_sd else None
+    vals = torch.empty(3, m, dtype=torch.float64, device=dev) if want_values else None
+    tki = torch.empty(3, max(k, 1), dtype=torch.int64, device=dev)
+    tkv = torch.empty(3, max(k, 1), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(L.mpo_gp_committee_score(com.models, com.E, ptr(c), m, float(y_opt), float(xi), float(kappa), flags,
+                                       ptr(mu), ptr(sd), ptr(vals), int(k), ptr(tki) if k else None,
+                                       ptr(tkv) if k else None, ptr(com._ws), com._ws.numel(),
+                                       _lib.stream_handle(dev)), "mpo_gp_committee_score")
+    out = {"mu": mu, "sd": sd, "values": {}, "topk": {}}
+    for a in acqs:
+        r = _lib.ACQ_ROW[a]
+        if vals is not None:
+            out["values"][a] = vals[r]
+        if k:
+            out["topk"][a] = (tki[r, :k], tkv[r, :k])
+    return out
+
+
+def acq_grad_committee(com, X, acq_codes, y_opt, xi=0.01, kappa=1.96):
+    """``mpo_gp_committee_grad_host``: :meth:`DeviceGP.acq_grad` under the committee's
+    posterior, through ``com``'s pinned round buffers.  Returns numpy ``(f (B,), g (B, d))``."""
+    r, B = _stage_round(com, X, acq_codes)
+    xp, ap, fp, gp = r.ptrs
+    rc = lib().mpo_gp_committee_grad_host(com.models, com.E, xp, B, ap, float(y_opt), float(xi), float(kappa), fp, gp,
+                                          com._ag_stream)
+    if rc != 0:
+        check(rc, "mpo_gp_committee_grad_host")
+    return r.fg(B)
+
+
+def polish_committee(com, starts, acq_codes, y_opt, xi, kappa, bounds, ftol, maxiter=20, gtol=1e-5, maxfun=15000):
+    """``mpo_gp_polish_committee_host``: :meth:`DeviceGP.polish` on the committee's objective.
+    Returns [(x, f)] per run."""
+    starts = _polish_starts(starts, com.d)
+    x, f, _, _ = _run_polish("mpo_gp_polish_committee_host", (com.models, com.E),
+                             (float(y_opt), float(xi), float(kappa)), starts, acq_codes, bounds, ftol, maxiter, gtol,
+                             maxfun, com._ensure_ag(len(starts)), com._ag_stream)
     return [(x[r], float(f[r])) for r in range(len(starts))]
 
 

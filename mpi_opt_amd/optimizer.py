@@ -59,11 +59,14 @@ class GPModel:
     """A fitted surrogate: hyper-parameters + its device posterior (rebuilt lazily,
     so the model pickles without device state)."""
 
-    def __init__(self, Xt, y, amp, length_scale, noise, device=None):
+    def __init__(self, Xt, y, amp, length_scale, noise, device=None, norm=None):
         self.Xt = np.asarray(Xt, dtype=float)
         self.y = np.asarray(y, dtype=float)
         self.amp, self.length_scale, self.noise = float(amp), np.asarray(length_scale, float), float(noise)
         self.device = device
+        # (y_mean, y_std) when the targets are normalised over more than this model's own
+        # values (an expert of a CommitteeModel); None: sklearn's normalize_y over ``y``
+        self.norm = norm
         self._dev = None
 
     def __getstate__(self):
@@ -76,7 +79,8 @@ class GPModel:
         if self._dev is None:
             from .gp import DeviceGP
 
-            self._dev = DeviceGP(self.Xt, self.y, self.amp, self.length_scale, self.noise, device=self.device)
+            self._dev = DeviceGP(self.Xt, self.y, self.amp, self.length_scale, self.noise, device=self.device,
+                                 norm=getattr(self, "norm", None))
         return self._dev
 
     def appended(self, x_t, y_all):
@@ -190,6 +194,139 @@ class PsModel:
             e.device = v
 
 
+#: Optimizer(surrogate=...): one exact GP (skopt) or a committee of experts past ``expert_size``
+SURROGATES = ("exact", "committee")
+#: the bounds of Optimizer(expert_size=...)
+EXPERT_SIZE_BOUNDS = (16, 2048)
+
+
+def committee_partition(n, expert_size):
+    """The experts' observation indices: E = ceil(n / expert_size) experts, observation i (in
+    told order) belongs to expert i mod E.  No RNG draw; the sizes differ by at most 1."""
+    E = -(-int(n) // int(expert_size))
+    return [np.arange(e, n, E) for e in range(E)]
+
+
+def summed_lml_objective(lmls):
+    """The refit objective of a committee: ``evaluate(thetas [B, d+2]) -> (lml [B], grad [B, d+2],
+    info [B])`` that sums the experts' ``evaluate`` (``DeviceLML.evaluate``: one
+    ``mpo_gp_lml_grad_host`` call per expert) in expert order, value and gradient alike.  Where
+    any expert's ``info`` is non-zero (its Cholesky failed) the row reports that expert's info,
+    lml = -inf and grad = 0, as one GP's objective does."""
+    def evaluate(thetas):
+        thetas = np.atleast_2d(np.asarray(thetas, dtype=np.float64))
+        lml, grad, info = lmls[0].evaluate(thetas)
+        lml, grad, info = np.array(lml, dtype=np.float64), np.array(grad, dtype=np.float64), np.array(info)
+        for e in lmls[1:]:
+            v, g, i = e.evaluate(thetas)
+            lml = lml + v
+            grad = grad + g
+            info = np.where(info != 0, info, i)
+        bad = info != 0
+        lml[bad] = -np.inf
+        grad[bad] = 0.0
+        return lml, grad, info
+
+    return evaluate
+
+
+def fit_committee_hyperparameters(Xt, y, parts, random_state=None, n_restarts_optimizer=2, device=None):
+    """One theta for all experts: the maximiser of sum_e LML_e(theta) over the experts'
+    observation sets ``parts`` (``committee_partition``), the targets normalised ONCE over all
+    values.  Bounds, start point, restart draws and L-BFGS-B settings are
+    ``fit_gp_hyperparameters``'s (``lockstep_lbfgsb`` over ``summed_lml_objective``).
+    Returns (amp, length_scale, noise)."""
+    from .gp_fit import DeviceLML, lockstep_lbfgsb, normalize_targets
+
+    Xt = np.asarray(Xt, dtype=np.float64)
+    yn, _, _ = normalize_targets(y)
+    lmls = [DeviceLML(Xt[p], yn[p], device=device) for p in parts]
+    return lockstep_lbfgsb(summed_lml_objective(lmls), Xt.shape[1], random_state, n_restarts_optimizer, driver=DRIVER)
+
+
+class CommitteeModel:
+    """The surrogate of ``Optimizer(surrogate="committee")`` once n > ``expert_size`` (NOT the
+    reference's semantics): a robust Bayesian committee machine (Deisenroth & Ng, ICML 2015)
+    of E = ceil(n / expert_size) exact GPs that share one theta.  ``estimators_`` are the
+    experts, each a :class:`GPModel` over the observations i = e (mod E), prepared with the
+    normalisation of ALL n targets.  ``predict`` combines them (``mpo_gp_committee_score``):
+    in normalised units, with r_e = v_e / amp clamped to [2^-52, 1] and b_e = -ln(r_e) / 2,
+    ``P = 1 + sum b_e (1 / r_e - 1)``, ``mu = y_mean + y_std (sum b_e m_e / r_e) / P`` and
+    ``sd = y_std sqrt(amp / P)``.  Pickles without device state."""
+
+    surrogate = "committee"
+
+    def __init__(self, Xt, y, amp, length_scale, noise, expert_size, device=None):
+        self.Xt = np.asarray(Xt, dtype=float)
+        self.y = np.asarray(y, dtype=float)
+        self.amp, self.length_scale, self.noise = float(amp), np.asarray(length_scale, float), float(noise)
+        self.expert_size = int(expert_size)
+        from .gp import _normalise
+
+        y_mean, y_std, _ = _normalise(self.y)
+        self.norm = (y_mean, y_std)
+        self.parts = committee_partition(len(self.y), self.expert_size)
+        if len(self.parts) < 2:
+            raise ValueError(f"a committee needs n > expert_size, got n = {len(self.y)}, expert_size = {expert_size}")
+        self.estimators_ = [GPModel(self.Xt[p], self.y[p], self.amp, self.length_scale, self.noise, device=device,
+                                    norm=self.norm) for p in self.parts]
+        self._com = None
+
+    def __getstate__(self):
+        d = dict(self.__dict__)
+        d["_com"] = None
+        return d
+
+    @property
+    def dev(self):
+        """The :class:`~mpi_opt_amd.gp.DeviceCommittee` over the experts' device posteriors."""
+        if self._com is None:
+            from .gp import DeviceCommittee
+
+            self._com = DeviceCommittee([e.dev for e in self.estimators_])
+        return self._com
+
+    # the optimizer releases and re-homes a model's device state through these two names
+    @property
+    def _dev(self):
+        return self._com
+
+    @_dev.setter
+    def _dev(self, v):
+        self._com = None
+        for e in self.estimators_:
+            e._dev = None
+
+    @property
+    def device(self):
+        return self.estimators_[0].device
+
+    @device.setter
+    def device(self, v):
+        for e in self.estimators_:
+            e.device = v
+
+    def predict_mean(self, X):
+        return self.predict(X)
+
+    def predict(self, X, return_std=False, return_cov=False):
+        """The committee's mean, or ``(mu, sd)``, at the rows of ``X`` (transformed space)."""
+        if return_cov:
+            raise ValueError('the "committee" surrogate has no joint posterior: return_cov is not supported')
+        from .gp import score_committee
+
+        out = score_committee(self.dev, np.atleast_2d(np.asarray(X, dtype=float)), 0.0, acqs=("EI",), k=0,
+                              want_values=False)
+        mu, sd = out["mu"].cpu().numpy(), out["sd"].cpu().numpy()
+        return (mu, sd) if return_std else mu
+
+    def sample_y(self, X, n_samples=1, random_state=0):
+        raise ValueError('the "committee" surrogate has no joint posterior: sample_y is not supported')
+
+    def sample_paths(self, n_samples=1, n_features=2048, random_state=0):
+        raise ValueError('the "committee" surrogate has no pathwise samples: sample_paths is not supported')
+
+
 #: the cost-aware acquisitions: the told results are (value, time) pairs
 PS_ACQS = ("EIps", "PIps")
 
@@ -225,17 +362,25 @@ def polish_lockstep(model, starts, acqs, y_opt, xi, kappa, bounds, maxiter=20, d
     runs.  ``driver="native"``: the whole polish in ``mpo_gp_polish_host`` (the host
     L-BFGS-B of libmpo.so, no GIL held); "scipy": scipy's setulb driven from
     Python.  A :class:`PsModel` with "EIps" / "PIps" runs takes the cost-aware objective
-    (``mpo_gp_polish_ps_host`` / ``mpo_gp_acq_ps_grad_host``; ``kappa`` unused).
+    (``mpo_gp_polish_ps_host`` / ``mpo_gp_acq_ps_grad_host``; ``kappa`` unused); a
+    :class:`CommitteeModel` the committee's (``mpo_gp_polish_committee_host`` /
+    ``mpo_gp_committee_grad_host``).
     Returns [(x, f)] per run."""
     from .gp_fit import FMIN_FTOL, _Lockstep, _setulb, lbfgsb_batched
 
     codes = np.array([acq_code(a) for a in acqs], dtype=np.int32)
     ps = isinstance(model, PsModel)
+    com = isinstance(model, CommitteeModel)
     if ps:
         from .gp import acq_grad_ps, polish_ps
 
         fdev, tdev = (e.dev for e in model.estimators_)
+    if com:
+        from .gp import acq_grad_committee, polish_committee
     if driver == "native":
+        if com:
+            return polish_committee(model.dev, np.array(starts), codes, y_opt, xi, kappa, bounds, ftol=FMIN_FTOL,
+                                    maxiter=maxiter)
         if ps:
             return polish_ps(fdev, tdev, np.array(starts), codes, y_opt, xi, bounds, ftol=FMIN_FTOL, maxiter=maxiter)
         return model.dev.polish(np.array(starts), codes, y_opt, xi, kappa, bounds, ftol=FMIN_FTOL, maxiter=maxiter)
@@ -245,6 +390,8 @@ def polish_lockstep(model, starts, acqs, y_opt, xi, kappa, bounds, maxiter=20, d
     def evaluate(X, ids):
         if ps:
             return acq_grad_ps(fdev, tdev, X, codes[ids], y_opt, xi)
+        if com:
+            return acq_grad_committee(model.dev, X, codes[ids], y_opt, xi, kappa)
         return model.dev.acq_grad(X, codes[ids], y_opt, xi, kappa)
 
     if _setulb() is not None:        # one thread drives every run (setulb reverse communication)
@@ -349,6 +496,25 @@ def _device_topk_ps(est, X, y_opt, acqs, xi, k):
     return out
 
 
+def _device_topk_committee(est, X, y_opt, acqs, xi, kappa, k):
+    """``blocks._device_topk`` for a :class:`CommitteeModel`: {acq: (values (k,), indices (k,))}
+    by ``mpo_gp_committee_score``; past MPO_TOPK_MAX a stable sort of the whole value rows."""
+    import torch
+
+    from .gp import score_committee
+
+    if k <= _lib.MPO_TOPK_MAX:
+        sc = score_committee(est.dev, X, y_opt, acqs=acqs, xi=xi, kappa=kappa, k=k, want_mu_sd=False,
+                             want_values=False)
+        return {a: (sc["topk"][a][1].cpu().numpy(), sc["topk"][a][0].cpu().numpy()) for a in acqs}
+    sc = score_committee(est.dev, X, y_opt, acqs=acqs, xi=xi, kappa=kappa, k=0, want_mu_sd=False, want_values=True)
+    out = {}
+    for a in acqs:
+        v, i = torch.sort(sc["values"][a], stable=True)
+        out[a] = (v[:k].cpu().numpy(), i[:k].cpu().numpy())
+    return out
+
+
 def _split_pairs(y, n):
     """The told results of a cost-aware acquisition as ``(values, log-times)``: one
     ``(value, time)`` pair (``n`` is None) or a sequence of ``n`` pairs.  ``ValueError`` for
@@ -383,9 +549,18 @@ CANDIDATES = ("host", "device")
 MAX_GP_POINTS = 2048
 
 
-def _check_gp_size(n_told, n_lies=0):
+def _check_gp_size(n_told, n_lies=0, expert_size=None):
     """One clear error before any device work when a refit would see more than
-    MAX_GP_POINTS observations: told points plus the lies of the running batch."""
+    MAX_GP_POINTS observations: told points plus the lies of the running batch.
+    ``expert_size`` (the "committee" surrogate): the bound is MPO_COMMITTEE_MAX experts of
+    that size instead."""
+    if expert_size is not None:
+        if n_told + n_lies > _lib.MPO_COMMITTEE_MAX * expert_size:
+            raise ValueError(
+                f"the committee surrogate takes at most {_lib.MPO_COMMITTEE_MAX} experts of expert_size = "
+                f"{expert_size} observations ({_lib.MPO_COMMITTEE_MAX * expert_size}), got n = {n_told + n_lies} "
+                f"({n_told} told points + {n_lies} constant-liar lies)")
+        return
     if n_told + n_lies > MAX_GP_POINTS:
         raise ValueError(
             f"the GP surrogate takes at most {MAX_GP_POINTS} observations, got n = {n_told + n_lies} "
@@ -781,6 +956,21 @@ class Optimizer:
     and of ``ti``.  No gp_hedge; a ``scorer`` is ignored (the asking rank scores locally);
     refused together with ``lie_refit="never"`` or the "thompson" strategy.
 
+    ``surrogate`` ("exact" | "committee", an addition of this build) and ``expert_size`` (an
+    int in [16, 2048], default 512): "exact" is skopt's one GP, which stops at 2048
+    observations.  "committee" departs from it once n > ``expert_size``: the told points are
+    split over E = ceil(n / expert_size) exact GPs (observation i, in told order, to expert
+    i mod E; no RandomState draw), the targets normalised once over all n values; one theta
+    maximises the sum of the experts' log-marginal likelihoods (the refit's bounds, starts and
+    L-BFGS-B settings), and the experts' predictions are combined as a robust Bayesian
+    committee machine (Deisenroth & Ng, ICML 2015; :class:`CommitteeModel`,
+    ``mpo_gp_committee_score`` / ``mpo_gp_committee_grad``).  While n <= ``expert_size`` every
+    fit and proposal is the "exact" one, bit for bit.  It takes up to 32 * ``expert_size``
+    observations.  Like a cost-aware acquisition it IGNORES a ``scorer``: the asking rank
+    scores all candidates locally.  The gp_hedge gains use the committee's mean.  Refused
+    together with ``lie_refit="never"``, the "thompson" strategy and "EIps" / "PIps".  NOT the
+    reference's semantics, and nothing is known about its effect on search quality.
+
     ``lie_refit`` ("every" | "never", an addition of this build): "every" is skopt's
     ``ask(n)``, a hyper-parameter refit per constant-liar lie.  "never" departs from it:
     the lies of a batch keep the theta of the copy's newest model and extend its
@@ -825,7 +1015,26 @@ class Optimizer:
                  initial_point_generator="random", acq_func="gp_hedge", acq_optimizer="auto",
                  random_state=None, model_queue_size=None, acq_func_kwargs=None, acq_optimizer_kwargs=None,
                  device=None, _gp_seed=None, scorer=None, chain_executor=None, lie_refit="every",
-                 candidates="host", batch_strategy="cl_min"):
+                 candidates="host", batch_strategy="cl_min", surrogate="exact", expert_size=512):
+        if surrogate not in SURROGATES:
+            raise ValueError(f"surrogate {surrogate!r}: one of {SURROGATES}")
+        if isinstance(expert_size, (bool, np.bool_)) or not isinstance(expert_size, (int, np.integer)) or \
+                not EXPERT_SIZE_BOUNDS[0] <= expert_size <= EXPERT_SIZE_BOUNDS[1]:
+            raise ValueError(f"expert_size {expert_size!r}: an int in [{EXPERT_SIZE_BOUNDS[0]}, "
+                             f"{EXPERT_SIZE_BOUNDS[1]}]")
+        if surrogate == "committee":
+            if lie_refit == "never":
+                raise ValueError('surrogate="committee" with lie_refit="never" is not supported: the fixed-theta '
+                                 "append extends one exact GP, a committee re-partitions its points")
+            if batch_strategy == "thompson":
+                raise ValueError('surrogate="committee" with the "thompson" strategy is not supported: a committee '
+                                 "has no joint posterior to draw from")
+            if acq_func in PS_ACQS:
+                raise ValueError(f'surrogate="committee" with acq_func {acq_func!r} is not supported: the cost-aware '
+                                 "acquisitions score two exact GPs")
+        # "exact": skopt's one GP.  "committee" (NOT the reference's semantics): past
+        # expert_size observations, an rBCM of ceil(n / expert_size) experts (CommitteeModel)
+        self.surrogate, self.expert_size = surrogate, int(expert_size)
         if batch_strategy not in STRATEGIES:
             raise ValueError(f"batch_strategy {batch_strategy!r}: one of {STRATEGIES}")
         # the strategy of ask(n) calls that name none (the reference's Coordinator.ask does
@@ -902,6 +1111,8 @@ class Optimizer:
         d.setdefault("candidates", "host")
         d.setdefault("batch_strategy", "cl_min")
         d.setdefault("ti", [])
+        d.setdefault("surrogate", "exact")
+        d.setdefault("expert_size", 512)
         self.__dict__.update(d)
 
     @property
@@ -915,7 +1126,13 @@ class Optimizer:
                     n_initial_points=self.n_initial_points_, initial_point_generator=self._initial_point_generator,
                     acq_func=self.acq_func, acq_optimizer=self.acq_optimizer, acq_func_kwargs=self.acq_func_kwargs,
                     acq_optimizer_kwargs=self.acq_optimizer_kwargs, _gp_seed=self._gp_seed,
-                    lie_refit=self.lie_refit, candidates=self.candidates, batch_strategy=self.batch_strategy)
+                    lie_refit=self.lie_refit, candidates=self.candidates, batch_strategy=self.batch_strategy,
+                    surrogate=self.surrogate, expert_size=self.expert_size)
+
+    @property
+    def _committee_size(self):
+        """``expert_size`` under the "committee" surrogate, else None (``_check_gp_size``)."""
+        return self.expert_size if self.surrogate == "committee" else None
 
     # ---- ask -------------------------------------------------------------------
     def copy(self, random_state=None):
@@ -930,6 +1147,8 @@ class Optimizer:
             raise ValueError(f"strategy {strategy!r}")
         if strategy == "thompson" and self._ps:
             raise ValueError(f'acq_func {self.acq_func!r} with the "thompson" strategy is not supported')
+        if strategy == "thompson" and self.surrogate == "committee":
+            raise ValueError('surrogate="committee" with the "thompson" strategy is not supported')
         if strategy == "thompson" and self.base_estimator_ == "gp":
             # refused here, before the copy's fit (_thompson_step checks again)
             thompson_config(self.acq_optimizer_kwargs, self.n_points, n_points - max(self._n_initial_points, 0))
@@ -937,7 +1156,7 @@ class Optimizer:
             return self.cache_[(n_points, strategy)]
         if self.base_estimator_ == "gp" and self._n_initial_points - n_points <= 0:
             # every lie is told to the copy, the last one too; a Thompson batch tells none
-            _check_gp_size(len(self.yi), 0 if strategy == "thompson" else n_points)
+            _check_gp_size(len(self.yi), 0 if strategy == "thompson" else n_points, self._committee_size)
         job = ChainJob(self, self.rng.randint(0, np.iinfo(np.int32).max), n_points, strategy)
         if self.chain_executor is not None:
             X = self.chain_executor.submit(job)
@@ -982,7 +1201,7 @@ class Optimizer:
         if self._ps and (logt is None or (len(logt) if batch else 1) != n_new):
             raise ValueError(f"acq_func {self.acq_func!r}: every told value needs its time")
         if fit and self._n_initial_points - n_new <= 0 and self.base_estimator_ == "gp":
-            _check_gp_size(len(self.yi) + n_new)        # before the points are taken: nothing changes on error
+            _check_gp_size(len(self.yi) + n_new, 0, self._committee_size)        # before the points are taken: nothing changes on error
         if batch:
             self.Xi.extend([list(v) for v in x])
             self.yi.extend([float(v) for v in y])
@@ -1007,6 +1226,16 @@ class Optimizer:
         Xt = self.space.transform(self.Xi)
         y = np.asarray(self.yi, dtype=float)
         t0 = time.perf_counter()
+        if self.surrogate == "committee" and len(y) > self.expert_size:
+            # one theta for all experts (the sum of their LMLs), then every expert's posterior
+            parts = committee_partition(len(y), self.expert_size)
+            amp, ls, noise = fit_committee_hyperparameters(Xt, y, parts, random_state=self._gp_seed,
+                                                           device=self.device)
+            t1 = time.perf_counter()
+            est = CommitteeModel(Xt, y, amp, ls, noise, self.expert_size, device=self.device)
+            est.dev                               # mpo_gp_prepare per expert, mpo_gp_committee_check
+            self._propose(est, t0, t1, time.perf_counter())
+            return
         amp, ls, noise = fit_gp_hyperparameters(Xt, y, random_state=self._gp_seed, device=self.device)
         if self._ps:
             # skopt's MultiOutputRegressor(clone(base_estimator)): the same estimator, so the
@@ -1066,6 +1295,8 @@ class Optimizer:
         if rec is not None and self._ps:
             tau = est.estimators_[1]
             rec["theta_t"] = (tau.amp, tau.length_scale.copy(), tau.noise)
+        if rec is not None and isinstance(est, CommitteeModel):
+            rec["experts"] = len(est.estimators_)
         if cand_seed is not None:
             # X stays the device tensor; the host sees the winning rows only
             won = _gather_winners(X, [top[a] for a in self.cand_acq_funcs_])
@@ -1114,10 +1345,13 @@ class Optimizer:
         ``n_restarts_optimizer`` takes the full value rows and a stable sort.  With
         a ``scorer`` (e.g. blocks.ShardedScorer) the candidates are split over GPUs.
         A cost-aware acquisition ("EIps" / "PIps") IGNORES the scorer: the asking rank
-        scores all candidates locally against both models (``mpo_gp_acq_ps_score``)."""
+        scores all candidates locally against both models (``mpo_gp_acq_ps_score``); so does
+        a :class:`CommitteeModel` (``mpo_gp_committee_score``)."""
         acqs = tuple(self.cand_acq_funcs_)
         if self._ps:
             return {a: idx for a, (vals, idx) in _device_topk_ps(est, X, y_opt, acqs, xi, k).items()}
+        if isinstance(est, CommitteeModel):
+            return {a: idx for a, (vals, idx) in _device_topk_committee(est, X, y_opt, acqs, xi, kappa, k).items()}
         if self.scorer is not None:
             return self.scorer(est, X, y_opt, acqs, xi, kappa, k)
         from .blocks import _device_topk

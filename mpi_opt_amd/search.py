@@ -125,6 +125,14 @@ def make_parser():
                         "from its picked candidate by L-BFGS-B (20 iterations) instead of stopping at the "
                         "candidate (NOT the reference's semantics; nothing is known about its effect on "
                         "search quality)")
+    p.add_argument("--surrogate", default="exact", choices=["exact", "committee"],
+                   help="the optimizer's surrogate: exact (one GP over all told points, skopt's and the reference's "
+                        "semantics; at most 2048 observations) or committee (NOT the reference's semantics: past "
+                        "--expert-size observations the points are split over ceil(n / expert-size) exact GPs that "
+                        "share one theta, combined as a robust Bayesian committee machine; up to 32 experts; "
+                        "nothing is known about its effect on search quality)")
+    p.add_argument("--expert-size", type=int, default=512, dest="expert_size", metavar="N",
+                   help="with --surrogate committee: the most observations of one expert (16 .. 2048)")
     p.add_argument("--acq-func", default="gp_hedge", choices=list(ACQ_FUNCS), dest="acq_func",
                    help="the optimizer's acquisition function (skopt's names; the reference's Coordinator uses the "
                         "default, gp_hedge).  EIps / PIps are skopt's cost-aware acquisitions: every result is told "
@@ -278,6 +286,10 @@ def run_search(args, x=None, y=None, log=print, progress=None, on_population=Non
         opt_kw["lie_refit"] = args.lie_refit              # fixed-theta ask batches (not skopt's semantics)
     if args.batch_strategy != "cl_min":
         opt_kw["batch_strategy"] = args.batch_strategy    # Thompson ask batches (not skopt's semantics)
+    if args.surrogate != "exact":
+        opt_kw["surrogate"] = args.surrogate              # a committee of experts (not skopt's semantics)
+    if args.expert_size != 512:
+        opt_kw["expert_size"] = args.expert_size
     if args.candidate_source != "host":
         opt_kw["candidates"] = args.candidate_source      # device-drawn candidates (not skopt's stream)
     if args.thompson_sampler != "joint":
