@@ -541,7 +541,10 @@ __device__ __forceinline__ void score_finish_own_rows(double* kc, int wave, int 
 // tile's candidate rows are staged into cs between them (cs is read only before B),
 // the rows of the tile after that load meanwhile, and the mu / q partials travel
 // through red without a barrier of their own (mu in two halves by tile parity; the
-// argument is at the two barriers).
+// argument is at the two barriers).  A wave runs at raised priority (s_setprio 2)
+// everywhere except phase 2's MFMA stream (priority 0): the CU's five workgroups are
+// independent, and what a wave does outside phase 2 is short VALU work that its three
+// siblings wait for at the next barrier.
 // FIN = 1 (every scoring launch): after its tile loop the workgroup finishes its own
 // candidates -- the (mu_n, q) rows it wrote (still largely in this XCD's L2) read
 // back 64 per wave with every lane live, the posterior and acquisitions as
@@ -633,6 +636,15 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
     int vs = (wave + (int)blockIdx.x) & 3;
     double* redm = red;   // this tile's mu rows; the other parity's: red + 4 * BM
 
+    // Static wave priority: raised everywhere but in phase 2's MFMA stream.  A CU holds
+    // the waves of five independent workgroups, each SIMD one wave of each.  A wave in
+    // phase 1, a fold or phase 3 runs a short VALU stretch that its three siblings on
+    // the other SIMDs wait for at the next barrier; a wave in phase 2 issues 64-cycle
+    // MFMAs back to back and loses little when the arbiter lets a sibling workgroup's
+    // VALU instruction through first.  Measured: -3.6% at the flagship shape, bits
+    // unchanged (DESIGN 3.1 "Wave priority by phase"; a third level for the folds and
+    // phase 3 measured the same as two).
+    __builtin_amdgcn_s_setprio(2);
     for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const long long m0 = tile * BM;
 
@@ -768,6 +780,7 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
     // (in the four-barrier loop, loading the ring's first groups before the barriers
     // instead measured the same).
     {
+        __builtin_amdgcn_s_setprio(0);   // behind the staging: the MFMA stream yields to the other workgroups' VALU phases
         double b0[4], b1[4];
         MPO_LD4(b0, bs);
         MPO_LD4(b1, bs + 256);
@@ -812,6 +825,7 @@ __global__ __launch_bounds__(256, OCC) void gp_score_kernel(ScoreArgs a) {
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(b0[0]), "+v"(b0[1]), "+v"(b0[2]), "+v"(b0[3]), "+v"(b1[0]),
                      "+v"(b1[1]), "+v"(b1[2]), "+v"(b1[3]));
 #undef MPO_EI_GROUP
+        __builtin_amdgcn_s_setprio(2);   // the q fold, barrier D, phase 3 and the next phase 1
         // f64 C/D map: col = lane & 15, row = (lane >> 4) + 4 r.  Sum the columns:
         // all four folds first, then the stores
         colsum16x4(sq);
