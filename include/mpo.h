@@ -931,6 +931,52 @@ int mpo_dn_set_active(void* handle, const uint8_t* active, void* stream);
  * arithmetic only): those of a plan of as many members as are active. */
 int mpo_dn_step_work(const void* handle, int64_t* workgroups, int64_t* launches);
 
+/* ------------------------------------------------------------------------
+ * Population training of the strided test_cnn, option3's `topclass` example
+ * (mpiLAPI.py:178-195, hyperparameter_search_option3.py:108-123, base_model.py:21-55):
+ *   Conv2D(32, k, strides 3, valid, relu) x 2 -> MaxPool 2x2 -> Dropout(dropout / 2)
+ *   -> Flatten (NHWC) -> Dense(128, relu) -> Dropout(dropout) -> Dense(classes, softmax).
+ * The input shape and the class count belong to the population; each member has its
+ * own kernel_size, dropout, lr, seed and loss / optimizer bits.
+ * ---------------------------------------------------------------------- */
+typedef struct MpoTcSpec {
+    int32_t kernel_size;  /* k 1..9 (option3: Integer(1, 6); CNNModel grid: 3..9)                 */
+    float lr;             /* learning rate of the trainer (the builder's llr never reaches it)   */
+    float dropout;        /* layer 0 drops dropout / 2, layer 1 dropout; a rate outside (0, 1)
+                             is the identity, as Keras 2's Dropout.call                          */
+    uint32_t seed;        /* dropout stream seed                                                 */
+    int32_t options;      /* MPO_LOSS_* | MPO_OPT_*                                              */
+} MpoTcSpec;
+
+/* Plan a population on x [n][H][W][C] with `classes` outputs (host only).  n_members >= 1,
+ * batch 1..256 (else MPO_EINVAL).  MPO_ENOTSUP, with the reason in mpo_last_error(), for
+ * H or W outside 1..256, C outside 1..8, classes outside 2..16, a kernel_size outside
+ * 1..9, a conv2 output ((in - k) / 3 + 1 per axis, twice) below 2 on either axis, lr <= 0,
+ * a non-finite lr / dropout or an unknown option bit.  Nothing is clamped. */
+int mpo_tc_create(const MpoTcSpec* specs, int n_members, int batch, int H, int W, int C, int classes, void** handle);
+int mpo_tc_destroy(void* handle);
+int mpo_tc_sizes(const void* handle, MpoPopSizes* out);
+/* offsets[9] (floats into the parameter arena) of member's w1 (k,k,C,32), b1, w2 (k,k,32,32),
+ * b2, w3 (Hp*Wp*32, 128), b3, w4 (128, classes), b4, end: Keras shapes and order, each
+ * tensor contiguous. */
+int mpo_tc_param_layout(const void* handle, int member, int64_t* offsets);
+/* offsets[12] (floats into the activation arena) of member's a1 [B,H1,W1,32], a2 [B,H2,W2,32],
+ * pd [B,K1], the pool argmax (int32 [B,K1]: 2 dy + dx), h, hd [B,128], z3, dz3 [B,classes],
+ * dh, dp, dz2, dz1 (diagnostics and tests). */
+int mpo_tc_act_layout(const void* handle, int member, int64_t* offsets);
+/* As mpo_pop_bind (arenas zero-initialised by the caller); waits for the table upload. */
+int mpo_tc_bind(void* handle, float* params, float* grads, float* adam_m, float* adam_v, float* act, void* tables,
+                void* stream);
+/* As mpo_pop_train_step / mpo_pop_eval_step, on x [n][H][W][C] f32: one update of every
+ * member on rows [row0, row0 + batch) of its order row (dropout masks from the counter
+ * hash at `step`, layer 0 after the pool, layer 1 after the dense layer; Adam t = step + 1);
+ * loss_out[member] = mean loss of the batch.  The eval step runs without dropout and
+ * accumulates loss_sum / correct. */
+int mpo_tc_train_step(void* handle, const float* x, const int32_t* labels, const int32_t* order,
+                      int64_t order_stride, int64_t row0, int32_t step, float* loss_out, void* stream);
+int mpo_tc_eval_step(void* handle, const float* x, const int32_t* labels, const int32_t* order,
+                     int64_t order_stride, int64_t row0, float* loss_sum, int32_t* correct, void* stream);
+
 /* k-fold index gather: out[r][:] = X[idx[r]][:] (the fold split
  * that mpi_learn does with per-fold communicators becomes an index gather). */
 int mpo_kfold_gather(const float* X, const int32_t* idx, int64_t rows, int row_elems, float* out,

@@ -104,6 +104,11 @@ class MpoDnSizes(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+class MpoTcSpec(ctypes.Structure):
+    _fields_ = [("kernel_size", ctypes.c_int32), ("lr", ctypes.c_float), ("dropout", ctypes.c_float),
+                ("seed", ctypes.c_uint32), ("options", ctypes.c_int32)]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _I64 = ctypes.c_int64
@@ -198,6 +203,14 @@ SIGNATURES = {
     "mpo_dn_penalty": (_I, [_P, _P, _P]),
     "mpo_dn_set_active": (_I, [_P, _P, _P]),
     "mpo_dn_step_work": (_I, [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "mpo_tc_create": (_I, [ctypes.POINTER(MpoTcSpec), _I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_void_p)]),
+    "mpo_tc_destroy": (_I, [_P]),
+    "mpo_tc_sizes": (_I, [_P, ctypes.POINTER(MpoPopSizes)]),
+    "mpo_tc_param_layout": (_I, [_P, _I, ctypes.POINTER(ctypes.c_int64)]),
+    "mpo_tc_act_layout": (_I, [_P, _I, ctypes.POINTER(ctypes.c_int64)]),
+    "mpo_tc_bind": (_I, [_P, _P, _P, _P, _P, _P, _P, _P]),
+    "mpo_tc_train_step": (_I, [_P, _P, _P, _P, _I64, _I64, ctypes.c_int32, _P, _P]),
+    "mpo_tc_eval_step": (_I, [_P, _P, _P, _P, _I64, _I64, _P, _P, _P]),
     "mpo_kfold_gather": (_I, [_P, _P, _I64, _I, _P, _P]),
 }
 

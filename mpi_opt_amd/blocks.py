@@ -95,7 +95,7 @@ class TrialEvaluator:
 
     def train_units(self, units, seed_base=0, trial_ids=None):
         """Train the given (trial, fold, spec) units as populations -- one for the
-        test_mnist units, one per DenseNet architecture; returns
+        test_mnist units, one per test_cnn input shape, one per DenseNet architecture; returns
         {(trial, fold): history dict}.  Trial ``t`` is seeded by its identity
         ``trial_ids[t]`` (default ``seed_base + t``)."""
         import time
@@ -109,10 +109,17 @@ class TrialEvaluator:
 
     def _train_units(self, units, tid):
         from .models import DenseNetSpec
+        from .topclass import TopclassSpec
 
         out = {}
-        mnist = [u for u in units if not isinstance(u[2], DenseNetSpec)]
+        mnist = [u for u in units if not isinstance(u[2], (DenseNetSpec, TopclassSpec))]
         out.update(self._train_mnist(mnist, tid))
+        shapes = {}
+        for u in units:
+            if isinstance(u[2], TopclassSpec):
+                shapes.setdefault((tuple(u[2].input_shape), int(u[2].classes)), []).append(u)
+        for us in shapes.values():
+            out.update(self._train_topclass(us, tid))
         groups = {}
         for u in units:
             if isinstance(u[2], DenseNetSpec):
@@ -141,6 +148,24 @@ class TrialEvaluator:
             init.append(glorot_uniform_init(s, uid))
         eng = PopulationEngine(specs, batch=self.batch, device=self.device, init=init)
         return self._histories(units, eng.fit_folds(self.x, self.y, folds, self.n_fold, self.epochs,
+                                                      holdout=self.holdout, progress=self._epoch_cb(len(units)),
+                                                      stopping=self.stopping, retire_stopped=self.retire_stopped))
+
+    def _train_topclass(self, units, tid):
+        """One population of test_cnn units on one input shape (topclass.py), trained with
+        the trainer's --loss / --optimizer like the test_mnist units."""
+        from .topclass import TopclassPopulation, TopclassSpec, glorot_uniform_init
+
+        specs, folds, init = [], [], []
+        for (t, f, spec, _) in units:
+            uid = self._uid(tid(t), f)
+            s = TopclassSpec(spec.kernel_size, spec.dropout, spec.lr, uid, spec.input_shape, spec.classes,
+                             loss=self.loss, optimizer=self.optimizer)
+            specs.append(s)
+            folds.append(f)
+            init.append(glorot_uniform_init(s, uid))
+        pop = TopclassPopulation(specs, batch=self.batch, device=self.device, init=init)
+        return self._histories(units, pop.fit_folds(self.x, self.y, folds, self.n_fold, self.epochs,
                                                       holdout=self.holdout, progress=self._epoch_cb(len(units)),
                                                       stopping=self.stopping, retire_stopped=self.retire_stopped))
 

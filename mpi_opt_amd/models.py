@@ -9,14 +9,18 @@
   the rate stays 0.25 -- reproduced here.
 * ``test_densenet`` -- mpiLAPI.py:197-201 (DenseNet) as a JSON spec that
   ingests into a :class:`DenseNetSpec` the DenseNet population engine
-  (densenet.py) trains.  The topclass CNN and the 3-D GAN (mpiLAPI.py:178-195,
-  option3:110-114, 144-168) are out of scope: their data and models
-  are not in the BASELINE configs, so no builder is offered for them.
+  (densenet.py) trains.
+* ``test_cnn`` -- mpiLAPI.py:178-195, the strided CNN of option3's ``topclass``
+  example (option3:108-123), as the Sequential JSON that ingests into a
+  :class:`~mpi_opt_amd.topclass.TopclassSpec` (topclass.py trains it); ``CNNModel``
+  (base_model.py:21-55) builds the same network.  Here ``dropout`` and
+  ``kernel_size`` are live; ``lr`` / ``llr`` are compiled into the model, which
+  ``to_json`` drops.  The 3-D GAN (option3:144-168) stays out of scope.
 * ``BuilderFromFunction`` -- hyperparameter_search_option3.py:22-31: zips the
   named dimensions with a parameter list, calls ``model_fn(**named)`` and wraps
   the JSON in a ``ModelFromJson`` with settable ``comm`` / ``device`` and
   ``get_device_name`` (used by process_block.py:64-67).
-* ``BaseModel`` / ``DenseNetModel`` -- base_model.py:8-19, 57-92:
+* ``BaseModel`` / ``CNNModel`` / ``DenseNetModel`` -- base_model.py:8-19, 21-55, 57-92:
   ``build(params) -> json``, ``get_parameter_grid()``, ``get_name()``.
 """
 from __future__ import annotations
@@ -71,6 +75,34 @@ def test_mnist(**args):
     return _sequential(layers)
 
 
+def test_cnn(**args):
+    """mpiLAPI.py:178-195: two strided valid convolutions, a 2x2 max-pool and two dense
+    layers on 150x94x5 images, activations inside the layers (8 layers).  ``lr`` /
+    ``llr`` are read as the reference reads them and, compiled into the optimizer that
+    ``to_json`` drops, never reach the JSON.  ``input_shape`` (an addition; the reference
+    fixes 150x94x5) builds the same network on other images."""
+    return _cnn_json(args.get("dropout", 0.5), args.get("kernel_size", 3), args.get("input_shape", (150, 94, 5)),
+                     lr=args.get("lr", np.exp(-args.get("llr", np.log(1. / 1e-3)))))
+
+
+def _cnn_json(dropout, kernel_size, input_shape, lr=None, nb_classes=3):
+    do, ks = float(dropout), int(kernel_size)
+    conv = dict(filters=32, kernel_size=[ks, ks], strides=[3, 3], padding="valid", data_format="channels_last",
+                activation="relu", use_bias=True, kernel_initializer="glorot_uniform", bias_initializer="zeros")
+    dense = dict(use_bias=True, kernel_initializer="glorot_uniform", bias_initializer="zeros")
+    layers = [
+        _layer("Conv2D", name="conv2d_1", batch_input_shape=[None] + [int(v) for v in input_shape], **conv),
+        _layer("Conv2D", name="conv2d_2", **conv),
+        _layer("MaxPooling2D", name="max_pooling2d_1", pool_size=[2, 2], strides=[2, 2], padding="valid"),
+        _layer("Dropout", name="dropout_1", rate=do / 2),
+        _layer("Flatten", name="flatten_1"),
+        _layer("Dense", name="dense_1", units=128, activation="relu", **dense),
+        _layer("Dropout", name="dropout_2", rate=do),
+        _layer("Dense", name="dense_2", units=nb_classes, activation="softmax", **dense),
+    ]
+    return _sequential(layers)
+
+
 def test_densenet(nb_classes=3, img_dim=(150, 94, 5), depth=10, nb_dense_block=3, growth_rate=12,
                   dropout_rate=0.00, nb_filter=16, lr=1e-3):
     """mpiLAPI.py:197-201: ``DenseNet(...)`` (densenet.py:135-196), compiled with
@@ -111,9 +143,12 @@ def spec_from_json(json_str, lr=1e-3, seed=0):
             raise ValueError(f"DenseNet population trains weight_decay 1e-4 (densenet.py:136), JSON has {wd}")
         return DenseNetSpec(arch, lr)
     if d.get("class_name") != "Sequential":
-        raise ValueError("population engine trains the test_mnist Sequential topology only")
+        raise ValueError("population engines train the test_mnist / test_cnn Sequential topologies and the "
+                         "functional DenseNet only")
     layers = d["config"]["layers"] if isinstance(d["config"], dict) else d["config"]
     kinds = [l["class_name"] for l in layers]
+    if kinds == _CNN_KINDS:
+        return _topclass_spec(layers, lr, seed)
     expect = ["Conv2D", "Activation", "Conv2D", "Activation", "MaxPooling2D", "Dropout", "Flatten", "Dense",
               "Activation", "Dropout", "Dense", "Activation"]
     if kinds != expect:
@@ -132,6 +167,45 @@ def spec_from_json(json_str, lr=1e-3, seed=0):
         raise ValueError(f"unsupported activations {acts}")
     return TrialSpec(nb_filters=F, kernel_size=k, pool_size=int(pool["pool_size"][0]), dense=int(d1["units"]),
                      lr=lr, dropout=float(dr1["rate"]), seed=seed)
+
+
+_CNN_KINDS = ["Conv2D", "Conv2D", "MaxPooling2D", "Dropout", "Flatten", "Dense", "Dropout", "Dense"]
+
+
+def _pair(v):
+    return [int(v), int(v)] if np.isscalar(v) else [int(t) for t in v]
+
+
+def _topclass_spec(layers, lr, seed):
+    """The test_cnn topology (mpiLAPI.py:178-195) -> TopclassSpec; its variants are refused."""
+    from .topclass import DENSE, FILTERS, TopclassSpec
+
+    c1, c2, pool, dr1, _, d1, dr2, d2 = (l["config"] for l in layers)
+    shape = c1.get("batch_input_shape")
+    if shape is None or len(shape) != 4:
+        raise ValueError("test_cnn topology without a [None, H, W, C] batch_input_shape")
+    k = _pair(c1["kernel_size"])
+    for c in (c1, c2):
+        if _pair(c["kernel_size"]) != k or k[0] != k[1]:
+            raise ValueError(f"unsupported test_cnn variant: kernel sizes {c1['kernel_size']} / {c2['kernel_size']}")
+        if _pair(c.get("strides", 1)) != [3, 3] or c.get("padding", "valid") != "valid":
+            raise ValueError("unsupported test_cnn variant: the population engine trains strides 3, valid padding")
+        if int(c["filters"]) != FILTERS or c.get("activation") != "relu":
+            raise ValueError(f"unsupported test_cnn variant: {FILTERS} relu filters per convolution")
+        if c.get("data_format", "channels_last") != "channels_last" or _pair(c.get("dilation_rate", 1)) != [1, 1]:
+            raise ValueError("unsupported test_cnn variant: channels_last, undilated convolutions")
+    if _pair(pool["pool_size"]) != [2, 2] or _pair(pool.get("strides") or pool["pool_size"]) != [2, 2] \
+            or pool.get("padding", "valid") != "valid":
+        raise ValueError("unsupported test_cnn variant: 2x2 valid max-pool")
+    if int(d1["units"]) != DENSE or d1.get("activation") != "relu" or d2.get("activation") != "softmax":
+        raise ValueError(f"unsupported test_cnn variant: Dense({DENSE}, relu) -> Dense(classes, softmax)")
+    rate = float(dr2["rate"])
+    if float(dr1["rate"]) != rate / 2:
+        raise ValueError("unsupported test_cnn variant: the first dropout rate is half the second")
+    spec = TopclassSpec(kernel_size=k[0], dropout=rate, lr=lr, seed=seed, input_shape=tuple(int(v) for v in shape[1:]),
+                        classes=int(d2["units"]))
+    spec.geometry()   # refuses shapes the kernels do not take
+    return spec
 
 
 class ModelFromJson:
@@ -174,6 +248,26 @@ class BaseModel:
         raise NotImplementedError
 
 
+class CNNModel(BaseModel):
+    """base_model.py:21-55: test_cnn's network on ``input_shape``, 3 classes."""
+
+    def __init__(self, input_shape=(150, 94, 5)):
+        self.input_shape = input_shape
+
+    def build(self, params):
+        """base_model.py:26-45: the lr dimension (10**params[2]) is compiled into the
+        model, which ``to_json`` drops.  The reference builds a functional ``Model``
+        whose ``Flatten(x)`` cannot run; the network it means is test_cnn's, returned
+        as that Sequential JSON."""
+        return _cnn_json(float(params[1]), int(params[0]), self.input_shape, lr=10.0 ** params[2])
+
+    def get_parameter_grid(self):
+        return [(3, 9), (.0, .5), (-5, 1)]
+
+    def get_name(self):
+        return "CNN_model"
+
+
 class DenseNetModel(BaseModel):
     """base_model.py:57-92."""
 
@@ -204,10 +298,17 @@ def mnist_space():
             Real(0.0, 1.0, name="dropout")]
 
 
+def topclass_space():
+    """option3:111-113."""
+    from .space import Integer, Real
+
+    return [Real(0.0, 1.0, name="dropout"), Integer(1, 6, name="kernel_size"), Real(1., 10., name="llr")]
+
+
 def flops_of_params(model_fn, names, params):
     spec = spec_from_json(model_fn(**dict(zip(names, params))))
     return spec.flops_per_sample_train()
 
 
-__all__ = ["test_mnist", "test_densenet", "spec_from_json", "DenseNetSpec", "ModelFromJson", "BuilderFromFunction",
-           "BaseModel", "DenseNetModel", "mnist_space"]
+__all__ = ["test_mnist", "test_cnn", "test_densenet", "spec_from_json", "DenseNetSpec", "ModelFromJson",
+           "BuilderFromFunction", "BaseModel", "CNNModel", "DenseNetModel", "mnist_space", "topclass_space"]

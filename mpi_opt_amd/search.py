@@ -78,14 +78,17 @@ def make_parser():
     # MI355X build additions
     p.add_argument("--world-size", type=int, default=21,
                    help="rank count of the reference's `mpirun -n` (sets concurrent trials)")
-    p.add_argument("--n-samples", type=int, default=60000, help="synthetic MNIST-shape samples")
+    p.add_argument("--n-samples", type=int, default=60000,
+                   help="synthetic samples: MNIST-shape (--example mnist) or 150x94x5 LCD-jet-shape images "
+                        "(--example topclass: 282 KB per sample on the device)")
     p.add_argument("--synthetic-labels", default="uniform", choices=["uniform", "learnable"],
                    dest="synthetic_labels",
                    help="labels of the synthetic data: uniform random (SURVEY §8d; a flat objective) or a "
                         "fixed random linear teacher on the pooled image (learnable; trials differ)")
     p.add_argument("--data-dir", default=None,
-                   help="directory of *.h5 files with `features` / `labels` (option3's mnist data, "
-                        "/bigdata/shared/mnist/*.h5); first 70%% of the files train, the rest validate")
+                   help="directory of *.h5 files: `features` / `labels` for --example mnist (option3's "
+                        "/bigdata/shared/mnist/*.h5), `Images` / `Labels` for --example topclass (option3's "
+                        "LCDJets_Remake files); first 70%% of the files train, the rest validate")
     p.add_argument("--lr", type=float, default=1e-3, help="Adam learning rate (mpi_learn default)")
     p.add_argument("--history-dir", default=None, help="write per-trial history JSON here")
     p.add_argument("--checkpoint", default="coordinator.pkl")
@@ -162,6 +165,25 @@ def modelled_cost_fn(provider):
     return lambda params: flops_of_params(provider.model_fn, names, params) * 1e-9
 
 
+#: --example -> (features_name, labels_name) of its *.h5 files (option3:122-123, 141-142)
+EXAMPLE_DATASETS = {"mnist": ("features", "labels"), "topclass": ("Images", "Labels")}
+
+
+def example_provider(example, input_shape=None):
+    """option3:108-133: the model provider of ``--example``.  ``input_shape`` (topclass
+    only): build test_cnn on images of that shape instead of the reference's 150x94x5."""
+    from .models import BuilderFromFunction, mnist_space, test_cnn, test_mnist, topclass_space
+
+    if example == "topclass":
+        import functools
+
+        fn = test_cnn if input_shape is None else functools.partial(test_cnn, input_shape=tuple(input_shape))
+        return BuilderFromFunction(model_fn=fn, parameters=topclass_space())
+    if example == "mnist":
+        return BuilderFromFunction(model_fn=test_mnist, parameters=mnist_space())
+    raise ValueError(f"example {example!r} has no population engine")
+
+
 def check_sanity(args):
     assert args.block_size > 1, "Block size must be at least 2 (master + worker)"
 
@@ -213,7 +235,6 @@ def run_search(args, x=None, y=None, log=print, progress=None, on_population=Non
 
     from .blocks import DistributedEvaluator, PopulationComm, ShardedScorer, TrialEvaluator
     from .chains import DistributedChainExecutor, ThreadChainExecutor
-    from .models import BuilderFromFunction, mnist_space, test_mnist
     from .population import synthetic_mnist
     from .scheduler import AskTellScheduler
 
@@ -235,7 +256,9 @@ def run_search(args, x=None, y=None, log=print, progress=None, on_population=Non
         # a caller that set up the group (bench.py) also chose this rank's device
         local = torch.cuda.current_device()
     dev = torch.device("cuda", local)
-    provider = BuilderFromFunction(model_fn=test_mnist, parameters=mnist_space())
+    example = getattr(args, "example", "mnist")
+    # caller-supplied topclass images set test_cnn's input shape (the reference fixes 150x94x5)
+    provider = example_provider(example, tuple(x.shape[1:]) if example == "topclass" and x is not None else None)
     holdout = None
     if x is None and args.data_dir:
         from .h5 import load_xy, split_files
@@ -243,12 +266,24 @@ def run_search(args, x=None, y=None, log=print, progress=None, on_population=Non
         import numpy as np
 
         train_list, val_list = split_files(args.data_dir)
-        (xt, yt), (xv, yv) = load_xy(train_list), load_xy(val_list)
+        if example == "topclass":
+            fn, ln = EXAMPLE_DATASETS[example]
+            (xt, yt), (xv, yv) = (load_xy(lst, features_name=fn, labels_name=ln) for lst in (train_list, val_list))
+            # load_xy flattens rows (NHWC order) and arg-maxes one-hot labels; test_cnn's input is 150x94x5
+            if xt.shape[1] != 150 * 94 * 5 or xv.shape[1] != 150 * 94 * 5:
+                raise ValueError(f"--example topclass: `Images` rows of {xt.shape[1]} values, not 150*94*5")
+            xt, xv = xt.reshape(-1, 150, 94, 5), xv.reshape(-1, 150, 94, 5)
+        else:
+            (xt, yt), (xv, yv) = load_xy(train_list), load_xy(val_list)
         holdout = len(yt)
         xh, yh = np.concatenate([xt, xv]), np.concatenate([yt, yv])
         x, y = torch.from_numpy(xh).to(dev), torch.from_numpy(yh).to(dev)
         log(f"data: {len(train_list)} train / {len(val_list)} validation files, {holdout} / "
             f"{len(yh) - holdout} samples")
+    if x is None and example == "topclass":
+        from .topclass import synthetic_topclass
+
+        x, y = synthetic_topclass(args.n_samples, seed=0, device=dev, labels=args.synthetic_labels)
     if x is None:
         x, y = synthetic_mnist(args.n_samples, seed=0, device=dev, labels=args.synthetic_labels)
     evaluator = TrialEvaluator(provider, x, y, n_fold=args.n_fold, epochs=args.epochs, batch=args.batch,
@@ -385,9 +420,9 @@ def main(argv=None):
         print("error: --thompson-polish needs --batch-strategy thompson --thompson-sampler paths "
               "(only a sample path is a function that can be minimised)", file=sys.stderr)
         return 2
-    if args.example != "mnist":
-        print(f"example {args.example!r}: its data ({'LCD jets' if args.example == 'topclass' else '3D GAN'}) "
-              "and model are outside the MNIST population engine", file=sys.stderr)
+    if args.example not in EXAMPLE_DATASETS:
+        print(f"example {args.example!r}: its data (3D GAN) and model are outside the population engines, "
+              f"which train the examples {sorted(EXAMPLE_DATASETS)}", file=sys.stderr)
         return 2
     num_blocks, left_over = block_layout(args.world_size, args.block_size)
     if left_over:
