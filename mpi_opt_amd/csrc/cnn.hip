@@ -31,6 +31,7 @@
 // v_mfma_f32_16x16x4_f32 (exact f32, the reference's precision).
 
 #include "mpo_internal.h"
+#include "pop_common.h"
 
 #include <algorithm>
 #include <cstring>
@@ -43,11 +44,12 @@
 
 namespace {
 
+using namespace mpo::pop;   // dropout hash, loss row + fold, update_range, the size / offset queries
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kImg = 28;
 constexpr int kClasses = 10;
-constexpr float kBceEps = 1e-7f;
 
 // ---- device member descriptor (mirrors the host plan) ----------------------
 struct Member {
@@ -99,25 +101,6 @@ struct StepArgs {
     int wgpair;              // wgrpb 2 and Ho = 2 (mod 4): a row pair as one K run (plan knob wgpair)
 };
 
-
-// ---- dropout counter hash (identical in oracle/cnn.py) ---------------------
-__device__ __forceinline__ unsigned lowbias32(unsigned x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-__device__ __forceinline__ unsigned drop_base(unsigned seed, int step, int layer) {
-    unsigned b = lowbias32(seed ^ (unsigned)(layer * 0x9E3779B9u));
-    return lowbias32(b ^ (unsigned)step);
-}
-
-__device__ __forceinline__ bool drop_keep(unsigned base, unsigned elem, unsigned thr) {
-    return (lowbias32(elem ^ base) >> 8) >= thr;
-}
 
 // LDS pixel strides chosen for conflict-free MFMA operand reads (ds_read_b32 banks
 // = dword index mod 32 per 32-lane half):
@@ -1310,78 +1293,17 @@ __global__ __launch_bounds__(256) void dense_kernel(StepArgs a, const GemmItem* 
 // One workgroup per member; one thread per sample row.
 // ============================================================================
 __global__ __launch_bounds__(256) void softmax_bce_kernel(StepArgs a, const MItem* __restrict__ items) {
-    __shared__ float red[256];
-    __shared__ int redc[256];
     const int member = items[blockIdx.x].member;
     const Member& mb = a.mem[member];
     const int B = a.B;
-    const int tid = threadIdx.x;
     float lsum = 0.f;
     int corr = 0;
-    for (int b = tid; b < B; b += 256) {
-        const float* z = a.act + mb.z3 + (long long)b * kClasses;
+    for (int b = threadIdx.x; b < B; b += 256) {
         const int sidx = a.order[(long long)member * a.order_stride + a.row0 + b];
-        const int y = a.labels[sidx];
-        float zm = z[0];
-        int am = 0;
-#pragma unroll
-        for (int c = 1; c < kClasses; ++c) if (z[c] > zm) { zm = z[c]; am = c; }
-        float e[kClasses], s = 0.f;
-#pragma unroll
-        for (int c = 0; c < kClasses; ++c) { e[c] = expf(z[c] - zm); s += e[c]; }
-        corr += (am == y);
-        if (mb.loss == MPO_LOSS_CCE) {
-            // Keras categorical_crossentropy: q = p / sum p, clipped target probability;
-            // d loss / d logits = live (q - onehot) / B (the DenseNet head's form)
-            float q[kClasses], S2 = 0.f;
-#pragma unroll
-            for (int c = 0; c < kClasses; ++c) { q[c] = e[c] / s; S2 += q[c]; }
-#pragma unroll
-            for (int c = 0; c < kClasses; ++c) q[c] /= S2;
-            const float qt = q[y];
-            lsum += -logf(fminf(fmaxf(qt, kBceEps), 1.f - kBceEps));
-            if (a.train) {
-                const float live = (qt >= kBceEps && qt <= 1.f - kBceEps) ? 1.f / (float)B : 0.f;
-                float* dz = a.act + mb.dz3 + (long long)b * kClasses;
-#pragma unroll
-                for (int c = 0; c < kClasses; ++c) dz[c] = live * (q[c] - (c == y ? 1.f : 0.f));
-            }
-            continue;
-        }
-        float l = 0.f, gdot = 0.f, gp[kClasses], pr[kClasses];
-#pragma unroll
-        for (int c = 0; c < kClasses; ++c) {
-            const float p = e[c] / s;
-            pr[c] = p;
-            const float t = (c == y) ? 1.f : 0.f;
-            const float pc = fminf(fmaxf(p, kBceEps), 1.f - kBceEps);
-            l += -(t * logf(pc) + (1.f - t) * logf(1.f - pc));
-            const bool inside = p > kBceEps && p < 1.f - kBceEps;
-            gp[c] = inside ? (pc - t) / (pc * (1.f - pc)) / (float)(kClasses * B) : 0.f;
-            gdot += gp[c] * p;
-        }
-        lsum += l / (float)kClasses;
-        if (a.train) {
-            float* dz = a.act + mb.dz3 + (long long)b * kClasses;
-#pragma unroll
-            for (int c = 0; c < kClasses; ++c) dz[c] = pr[c] * (gp[c] - gdot);
-        }
+        softmax_loss_row<kClasses>(a.act + mb.z3 + (long long)b * kClasses, kClasses, a.labels[sidx], mb.loss, B, a.train,
+                                   a.act + mb.dz3 + (long long)b * kClasses, lsum, corr);
     }
-    red[tid] = lsum;
-    redc[tid] = corr;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) { red[tid] += red[tid + s]; redc[tid] += redc[tid + s]; }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        if (a.train) {
-            a.loss_out[member] = red[0] / (float)B;
-        } else {
-            a.loss_sum[member] += red[0];
-            a.correct[member] += redc[0];
-        }
-    }
+    loss_finish(lsum, corr, B, a.train, a.loss_out + member, a.loss_sum + member, a.correct + member);
 }
 
 // ============================================================================
@@ -1425,20 +1347,7 @@ __global__ __launch_bounds__(256) void adam_kernel(StepArgs a, const MItem* __re
     const Member& mb = a.mem[it.member];
     const long long begin = mb.w1 + (long long)it.aux * chunk;
     const long long end = min(mb.pend, begin + chunk);
-    if (mb.opt == MPO_OPT_SGD) {            // Keras SGD, no momentum
-        for (long long i = begin + threadIdx.x; i < end; i += blockDim.x) params[i] -= mb.lr * a.grads[i];
-        return;
-    }
-    const double corr = sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t));
-    const float lr_t = (float)(mb.lr * corr);
-    for (long long i = begin + threadIdx.x; i < end; i += blockDim.x) {
-        const float g = a.grads[i];
-        const float m = b1 * mo[i] + (1.f - b1) * g;
-        const float v = b2 * vo[i] + (1.f - b2) * g * g;
-        mo[i] = m;
-        vo[i] = v;
-        params[i] -= lr_t * m / (sqrtf(v) + eps);
-    }
+    update_range(params, a.grads, mo, vo, begin, end, mb.lr, mb.opt, t, b1, b2, eps);
 }
 
 __global__ void kfold_gather_kernel(const float* __restrict__ X, const int* __restrict__ idx, long long rows, int row_elems,
@@ -2276,11 +2185,7 @@ int mpo_pop_destroy(void* handle) {
 int mpo_pop_sizes(const void* handle, MpoPopSizes* out) {
     MPO_CHECK_ARG(handle && out, "mpo_pop_sizes: null pointer");
     const Plan& P = *static_cast<const Plan*>(handle);
-    out->n_params = P.n_params;
-    out->act_floats = P.act_floats;
-    out->table_bytes = (int64_t)P.table_bytes;
-    out->n_members = P.n;
-    out->batch = P.B;
+    fill_sizes(P, out);
     return MPO_OK;
 }
 
@@ -2290,7 +2195,7 @@ int mpo_pop_param_layout(const void* handle, int member, int64_t* offsets) {
     MPO_CHECK_ARG(member >= 0 && member < P.n, "mpo_pop_param_layout: member %d out of range", member);
     const Member& m = P.mem[member];
     const long long o[9] = {m.w1, m.b1, m.w2, m.b2, m.w3, m.b3, m.w4, m.b4, m.pend};
-    for (int i = 0; i < 9; ++i) offsets[i] = o[i];
+    copy_offsets(o, offsets);
     return MPO_OK;
 }
 
@@ -2300,7 +2205,7 @@ int mpo_pop_act_layout(const void* handle, int member, int64_t* offsets) {
     MPO_CHECK_ARG(member >= 0 && member < P.n, "mpo_pop_act_layout: member %d out of range", member);
     const Member& m = P.mem[member];
     const long long o[15] = {m.a1, m.a2, m.pd, m.am, m.h, m.hd, m.z3, m.dz3, m.dh, m.dp, m.dz2, m.dz1, m.w2t, m.wp1, m.wp2};
-    for (int i = 0; i < 15; ++i) offsets[i] = o[i];
+    copy_offsets(o, offsets);
     return MPO_OK;
 }
 

@@ -36,6 +36,7 @@
 //   adam                      Keras Adam / SGD with the member's lr
 
 #include "mpo_internal.h"
+#include "pop_common.h"
 
 #include <cmath>
 #include <cstring>
@@ -44,13 +45,14 @@
 
 namespace {
 
+using namespace mpo::pop;   // dropout hash, loss row + fold, update_range, the size / offset queries
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kF = 32;          // filters of both convolutions (mpiLAPI.py:184-185)
 constexpr int kD = 128;         // dense units (mpiLAPI.py:190)
 constexpr int kMaxClasses = 16;
 constexpr int kStride = 3;
-constexpr float kClipEps = 1e-7f;
 constexpr int kWgChunk = 2048;  // pixels per weight-gradient slab (a multiple of 4)
 constexpr int kAdamChunk = 4096;
 constexpr int kTileM = 64, kTileN = 32;
@@ -88,30 +90,11 @@ struct TcArgs {
 enum TcOp { CONV1_FWD = 0, CONV2_FWD, D1_FWD, D2_FWD, D2_WGRAD, D2_DGRAD, D1_WGRAD, D1_DGRAD, CONV2_DGRAD,
             CONV2_WGRAD, CONV1_WGRAD, kNumOps };
 
-// ---- dropout counter hash (identical in oracle/cnn.py and csrc/cnn.hip) -----
-__device__ __forceinline__ unsigned tc_lowbias32(unsigned x) {
-    x ^= x >> 16;
-    x *= 0x7feb352du;
-    x ^= x >> 15;
-    x *= 0x846ca68bu;
-    x ^= x >> 16;
-    return x;
-}
-
-__device__ __forceinline__ unsigned tc_drop_base(unsigned seed, int step, int layer) {
-    unsigned b = tc_lowbias32(seed ^ (unsigned)(layer * 0x9E3779B9u));
-    return tc_lowbias32(b ^ (unsigned)step);
-}
-
-__device__ __forceinline__ bool tc_drop_keep(unsigned base, unsigned elem, unsigned thr) {
-    return (tc_lowbias32(elem ^ base) >> 8) >= thr;
-}
-
 // multiplier of dropout `layer` on flat element `elem` of the member's [B, features] tensor
 __device__ __forceinline__ float tc_mask(const TcArgs& a, const TcMember& mb, int layer, unsigned elem) {
     if (!a.train || !(layer ? mb.drop1 : mb.drop0)) return 1.f;
-    const unsigned base = tc_drop_base(mb.seed, a.step, layer);
-    return tc_drop_keep(base, elem, layer ? mb.thr1 : mb.thr0) ? (layer ? mb.inv1 : mb.inv0) : 0.f;
+    const unsigned base = drop_base(mb.seed, a.step, layer);
+    return drop_keep(base, elem, layer ? mb.thr1 : mb.thr0) ? (layer ? mb.inv1 : mb.inv0) : 0.f;
 }
 
 // ============================================================================
@@ -364,72 +347,16 @@ __global__ __launch_bounds__(256) void tc_pool_bwd_kernel(TcArgs a) {
 // cce_loss_and_grad with the class count in place of 10).  A workgroup per member, a thread
 // per sample row.
 __global__ __launch_bounds__(256) void tc_loss_kernel(TcArgs a) {
-    __shared__ float red[256];
-    __shared__ int redc[256];
-    const int member = blockIdx.x, tid = threadIdx.x, B = a.B, nc = a.classes;
+    const int member = blockIdx.x, B = a.B, nc = a.classes;
     const TcMember& mb = a.mem[member];
     float lsum = 0.f;
     int corr = 0;
-    for (int b = tid; b < B; b += 256) {
-        const float* z = a.act + mb.z3 + (long long)b * nc;
+    for (int b = threadIdx.x; b < B; b += 256) {
         const int y = a.labels[a.order[(long long)member * a.order_stride + a.row0 + b]];
-        float zm = z[0];
-        int am = 0;
-        for (int c = 1; c < nc; ++c) if (z[c] > zm) { zm = z[c]; am = c; }
-        float e[kMaxClasses], s = 0.f;
-#pragma unroll
-        for (int c = 0; c < kMaxClasses; ++c) { e[c] = c < nc ? expf(z[c] - zm) : 0.f; s += e[c]; }
-        corr += (am == y);
-        float* dz = a.act + mb.dz3 + (long long)b * nc;
-        if (mb.loss == MPO_LOSS_CCE) {
-            float q[kMaxClasses], S2 = 0.f, qt = 0.f;
-#pragma unroll
-            for (int c = 0; c < kMaxClasses; ++c) { q[c] = e[c] / s; S2 += q[c]; }
-#pragma unroll
-            for (int c = 0; c < kMaxClasses; ++c) { q[c] /= S2; if (c == y) qt = q[c]; }
-            lsum += -logf(fminf(fmaxf(qt, kClipEps), 1.f - kClipEps));
-            if (a.train) {
-                const float live = (qt >= kClipEps && qt <= 1.f - kClipEps) ? 1.f / (float)B : 0.f;
-#pragma unroll
-                for (int c = 0; c < kMaxClasses; ++c) if (c < nc) dz[c] = live * (q[c] - (c == y ? 1.f : 0.f));
-            }
-            continue;
-        }
-        float l = 0.f, gdot = 0.f, gp[kMaxClasses], pr[kMaxClasses];
-#pragma unroll
-        for (int c = 0; c < kMaxClasses; ++c) {
-            gp[c] = pr[c] = 0.f;
-            if (c >= nc) continue;
-            const float p = e[c] / s;
-            pr[c] = p;
-            const float t = (c == y) ? 1.f : 0.f;
-            const float pc = fminf(fmaxf(p, kClipEps), 1.f - kClipEps);
-            l += -(t * logf(pc) + (1.f - t) * logf(1.f - pc));
-            const bool inside = p > kClipEps && p < 1.f - kClipEps;
-            gp[c] = inside ? (pc - t) / (pc * (1.f - pc)) / (float)(nc * B) : 0.f;
-            gdot += gp[c] * p;
-        }
-        lsum += l / (float)nc;
-        if (a.train) {
-#pragma unroll
-            for (int c = 0; c < kMaxClasses; ++c) if (c < nc) dz[c] = pr[c] * (gp[c] - gdot);
-        }
+        softmax_loss_row<kMaxClasses>(a.act + mb.z3 + (long long)b * nc, nc, y, mb.loss, B, a.train,
+                                      a.act + mb.dz3 + (long long)b * nc, lsum, corr);
     }
-    red[tid] = lsum;
-    redc[tid] = corr;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) { red[tid] += red[tid + s]; redc[tid] += redc[tid + s]; }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        if (a.train) {
-            a.loss_out[member] = red[0] / (float)B;
-        } else {
-            a.loss_sum[member] += red[0];
-            a.correct[member] += redc[0];
-        }
-    }
+    loss_finish(lsum, corr, B, a.train, a.loss_out + member, a.loss_sum + member, a.correct + member);
 }
 
 // weight-gradient slabs -> dw, db (slab order).  conv: 0 = conv1, 1 = conv2
@@ -453,21 +380,7 @@ __global__ __launch_bounds__(256) void tc_adam_kernel(TcArgs a, float* __restric
     const long long begin = mb.w1 + (long long)blockIdx.x * kAdamChunk;
     const long long end = min(mb.pend, begin + kAdamChunk);
     if (begin >= end) return;
-    if (mb.opt == MPO_OPT_SGD) {
-        for (long long i = begin + threadIdx.x; i < end; i += 256) a.params[i] -= mb.lr * a.grads[i];
-        return;
-    }
-    const float b1 = 0.9f, b2 = 0.999f, eps = 1e-8f;
-    const double corr = sqrt(1.0 - pow((double)b2, t)) / (1.0 - pow((double)b1, t));
-    const float lr_t = (float)(mb.lr * corr);
-    for (long long i = begin + threadIdx.x; i < end; i += 256) {
-        const float g = a.grads[i];
-        const float m = b1 * mo[i] + (1.f - b1) * g;
-        const float v = b2 * vo[i] + (1.f - b2) * g * g;
-        mo[i] = m;
-        vo[i] = v;
-        a.params[i] -= lr_t * m / (sqrtf(v) + eps);
-    }
+    update_range(a.params, a.grads, mo, vo, begin, end, mb.lr, mb.opt, t, 0.9f, 0.999f, 1e-8f);
 }
 
 // ============================================================================
@@ -687,11 +600,7 @@ int mpo_tc_destroy(void* handle) {
 int mpo_tc_sizes(const void* handle, MpoPopSizes* out) {
     MPO_CHECK_ARG(handle && out, "mpo_tc_sizes: null pointer");
     const TcPlan& P = *static_cast<const TcPlan*>(handle);
-    out->n_params = P.n_params;
-    out->act_floats = P.act_floats;
-    out->table_bytes = (int64_t)P.table_bytes;
-    out->n_members = P.n;
-    out->batch = P.B;
+    fill_sizes(P, out);
     return MPO_OK;
 }
 
@@ -701,7 +610,7 @@ int mpo_tc_param_layout(const void* handle, int member, int64_t* offsets) {
     MPO_CHECK_ARG(member >= 0 && member < P.n, "mpo_tc_param_layout: member %d out of range", member);
     const TcMember& m = P.mem[member];
     const long long o[9] = {m.w1, m.b1, m.w2, m.b2, m.w3, m.b3, m.w4, m.b4, m.pend};
-    for (int i = 0; i < 9; ++i) offsets[i] = o[i];
+    copy_offsets(o, offsets);
     return MPO_OK;
 }
 
@@ -711,7 +620,7 @@ int mpo_tc_act_layout(const void* handle, int member, int64_t* offsets) {
     MPO_CHECK_ARG(member >= 0 && member < P.n, "mpo_tc_act_layout: member %d out of range", member);
     const TcMember& m = P.mem[member];
     const long long o[12] = {m.a1, m.a2, m.pd, m.am, m.h, m.hd, m.z3, m.dz3, m.dh, m.dp, m.dz2, m.dz1};
-    for (int i = 0; i < 12; ++i) offsets[i] = o[i];
+    copy_offsets(o, offsets);
     return MPO_OK;
 }
 

@@ -25,8 +25,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, lib, ptr
-from .population import _set_active, _step_work, kfold_split, train_folds  # noqa: F401 (kfold_split re-exported)
+from ._lib import ptr
+from .population import _PopulationBase, _Retirable, kfold_split, train_folds  # noqa: F401 (the last two re-exported)
 
 KIND_NAMES = {0: "conv0", 1: "dense", 2: "trans", 3: "head"}
 
@@ -240,28 +240,24 @@ def hbm_bytes_train_by_kernel(layers, batch, n_params):
     return out
 
 
-class DenseNetPopulation:
+class DenseNetPopulation(_Retirable, _PopulationBase):
     """``n`` same-architecture DenseNet members resident on one GPU."""
+
+    _C = "mpo_dn"
 
     def __init__(self, arch: DenseNetArch, lrs, batch=100, device=None, init=None, init_seed=0):
         self.arch = arch
         self.lrs = np.asarray(lrs, dtype=np.float32).reshape(-1)
-        self.n = int(self.lrs.size)
-        self.batch = int(batch)
-        self.device = torch.device(device if device is not None else "cuda")
-        L = lib()
-        h = ctypes.c_void_p()
         a = arch.c_struct()
-        check(L.mpo_dn_create(ctypes.byref(a), self.n, self.batch, ctypes.byref(h)), "mpo_dn_create")
-        self._h = h
+        self._create(self.lrs.size, batch, device, ctypes.byref(a))
         sz = _lib.MpoDnSizes()
-        check(L.mpo_dn_sizes(h, ctypes.byref(sz)), "mpo_dn_sizes")
+        self._call("sizes", ctypes.byref(sz))
         self.n_params, self.n_state = int(sz.n_params), int(sz.n_state)
         self.layers, self._offs = [], []
         geom = (ctypes.c_int32 * 8)()
         offs = (ctypes.c_int64 * 6)()
         for i in range(int(sz.n_layers)):
-            check(L.mpo_dn_layer(h, i, geom, offs), "mpo_dn_layer")
+            self._call("layer", i, geom, offs)
             g = [int(v) for v in geom]
             self.layers.append(dict(kind=KIND_NAMES[g[0]], stage=g[1], H=g[2], W=g[3], cin=g[4], cout=g[5], ks=g[6],
                                     coff=g[7]))
@@ -288,41 +284,16 @@ class DenseNetPopulation:
         self.adam_v = torch.zeros_like(self.params)
         self.state = torch.zeros(self.n, self.n_state, dtype=torch.float32, device=dev)
         self.act = torch.zeros(int(sz.act_floats), dtype=torch.float32, device=dev)
-        self.loss = torch.zeros(self.n, dtype=torch.float32, device=dev)
-        self.val_loss_sum = torch.zeros(self.n, dtype=torch.float32, device=dev)
-        self.val_correct = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self._alloc_results()
         self._pen = torch.zeros(self.n, dtype=torch.float32, device=dev)
         lr_host = (ctypes.c_float * self.n)(*[float(v) for v in self.lrs])
-        with torch.cuda.device(dev):
-            check(L.mpo_dn_bind(h, ptr(self.params), ptr(self.grads), ptr(self.adam_m), ptr(self.adam_v),
-                                ptr(self.state), ptr(self.act), ctypes.cast(lr_host, ctypes.c_void_p),
-                                _lib.stream_handle(dev)), "mpo_dn_bind")
+        self._enqueue("bind", ptr(self.params), ptr(self.grads), ptr(self.adam_m), ptr(self.adam_v), ptr(self.state),
+                      ptr(self.act), ctypes.cast(lr_host, ctypes.c_void_p))
         if init is None:
             init = [he_uniform_init(self.layers, init_seed + i) for i in range(self.n)]
         for i, (p, s) in enumerate(init):
             self.set_params(i, p, s)
-        self.step_count = 0
         self.active = np.ones(self.n, dtype=bool)
-
-    # -- retiring members ---------------------------------------------------------
-    def set_active(self, mask):
-        """``mpo_dn_set_active``: as :meth:`PopulationEngine.set_active` -- retired
-        members cost no kernel work and keep their parameters, Adam and BN state and
-        ``loss`` / ``val_*`` entries (:meth:`penalty` still covers every member)."""
-        self.active = _set_active(self, lib().mpo_dn_set_active, mask)
-
-    def step_work(self):
-        """(workgroups, launches) of one train step under the current mask."""
-        return _step_work(self, lib().mpo_dn_step_work)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                lib().mpo_dn_destroy(h)
-            except Exception:
-                pass
-            self._h = None
 
     # -- parameters ---------------------------------------------------------------
     def set_params(self, i, params, state=None):
@@ -351,46 +322,12 @@ class DenseNetPopulation:
         return {n: host[self._sslots[n]:self._sslots[n] + int(np.prod(s))].reshape(s).copy()
                 for n, s in self.state_shapes.items()}
 
-    def reset_optimizer(self):
-        self.adam_m.zero_()
-        self.adam_v.zero_()
-        self.step_count = 0
-
-    # -- steps --------------------------------------------------------------------
-    def train_step(self, x, labels, order, row0, step=None):
-        """x [n,H,W,C] f32, labels [n] i32, order [n_members, L] i32 (device)."""
-        step = self.step_count if step is None else int(step)
-        with torch.cuda.device(self.device):
-            check(lib().mpo_dn_train_step(self._h, ptr(x), ptr(labels), ptr(order), int(order.shape[1]), int(row0),
-                                          step, ptr(self.loss), _lib.stream_handle(self.device)),
-                  "mpo_dn_train_step")
-        self.step_count = step + 1
-        return self.loss
-
-    def eval_reset(self):
-        self.val_loss_sum.zero_()
-        self.val_correct.zero_()
-
-    def eval_step(self, x, labels, order, row0):
-        with torch.cuda.device(self.device):
-            check(lib().mpo_dn_eval_step(self._h, ptr(x), ptr(labels), ptr(order), int(order.shape[1]), int(row0),
-                                         ptr(self.val_loss_sum), ptr(self.val_correct),
-                                         _lib.stream_handle(self.device)), "mpo_dn_eval_step")
-
     def penalty(self):
         """Per-member l2 penalty 1e-4 * sum w^2 of the current weights."""
-        with torch.cuda.device(self.device):
-            check(lib().mpo_dn_penalty(self._h, ptr(self._pen), _lib.stream_handle(self.device)), "mpo_dn_penalty")
+        self._enqueue("penalty", ptr(self._pen))
         return self._pen
 
-    # -- full k-fold training -----------------------------------------------------
-    def fit_folds(self, x, labels, folds, n_fold, epochs, record_train_loss=False, holdout=None, progress=None,
-                  stopping=None, retire_stopped=False):
-        """Train every member for ``epochs`` on its fold (in order, no shuffle),
-        validating once per epoch; val_loss = mean CE + l2 penalty (Keras).  The
-        loop is population.train_folds (``retire_stopped`` as there)."""
-        return train_folds(self, x, labels, folds, n_fold, epochs, record_train_loss, holdout, progress, stopping,
-                           val_offset=self.penalty, retire_stopped=retire_stopped)
+    _val_offset = penalty   # fit_folds: val_loss = mean CE + l2 penalty (Keras)
 
 
 def synthetic_cifar(n=50000, img_dim=(32, 32, 3), classes=10, seed=0, device=None):

@@ -32,6 +32,17 @@ PARAM_NAMES = ("w1", "b1", "w2", "b2", "w3", "b3", "w4", "b4")
 ACT_NAMES = ("a1", "a2", "pd", "am", "h", "hd", "z3", "dz3", "dh", "dp", "dz2", "dz1", "w2t", "wp1", "wp2")
 
 
+def spec_options(spec):
+    """``options`` bits of a member spec (MpoCnnSpec / MpoTcSpec: MPO_LOSS_* | MPO_OPT_*); raises for a
+    loss / optimizer the kernels do not implement.  ``TrialSpec.options`` and ``TopclassSpec.options``."""
+    try:
+        return _lib.LOSS_CODES[spec.loss] | _lib.OPT_CODES[spec.optimizer]
+    except KeyError:
+        raise ValueError(f"unsupported loss / optimizer {spec.loss!r} / {spec.optimizer!r}: the population "
+                         f"kernels implement losses {sorted(_lib.LOSS_CODES)} and optimizers "
+                         f"{sorted(_lib.OPT_CODES)}") from None
+
+
 @dataclass
 class TrialSpec:
     """One test_mnist trial (mpiLAPI.py:138-176; space option3:127-131)."""
@@ -46,14 +57,7 @@ class TrialSpec:
     loss: str = "binary_crossentropy"     # option3 --loss (:61)
     optimizer: str = "adam"               # option3 --optimizer (:60), the master's update rule
 
-    def options(self):
-        """MpoCnnSpec.options bits; raises for a loss / optimizer the kernels do not implement."""
-        try:
-            return _lib.LOSS_CODES[self.loss] | _lib.OPT_CODES[self.optimizer]
-        except KeyError:
-            raise ValueError(f"unsupported loss / optimizer {self.loss!r} / {self.optimizer!r}: the population "
-                             f"kernels implement losses {sorted(_lib.LOSS_CODES)} and optimizers "
-                             f"{sorted(_lib.OPT_CODES)}") from None
+    options = spec_options
 
     def geometry(self):
         H1 = IMG - self.kernel_size + 1
@@ -127,21 +131,15 @@ class TrialSpec:
         return {name: 4.0 * v for name, v in per.items()}
 
 
-MpoCnnSpec = _lib.MpoCnnSpec
-MpoPopSizes = _lib.MpoPopSizes
-
-
-def glorot_uniform_init(spec: TrialSpec, seed: int):
-    """Keras defaults: glorot_uniform kernels, zero biases (float32)."""
+def glorot_uniform_init(spec, seed: int):
+    """Keras defaults for a :class:`TrialSpec` or a ``TopclassSpec``: glorot_uniform kernels
+    (fan = receptive field x channels), zero biases (float32)."""
     rng = np.random.RandomState(seed)
     out = {}
     for name, shape in spec.param_shapes().items():
         if name.startswith("w"):
-            if len(shape) == 4:
-                rf = shape[0] * shape[1]
-                fan_in, fan_out = rf * shape[2], rf * shape[3]
-            else:
-                fan_in, fan_out = shape
+            rf = shape[0] * shape[1] if len(shape) == 4 else 1
+            fan_in, fan_out = rf * shape[-2], rf * shape[-1]
             lim = np.sqrt(6.0 / (fan_in + fan_out))
             out[name] = rng.uniform(-lim, lim, size=shape).astype(np.float32)
         else:
@@ -172,35 +170,133 @@ def kfold_split(n_samples: int, n_fold: int, fold: int, holdout=None):
     return np.concatenate([idx[:v0], idx[v1:]]), idx[v0:v1]
 
 
-class PopulationEngine:
-    """A population of ragged CNN members resident on one GPU."""
+class _PopulationBase:
+    """What the MNIST, topclass and DenseNet populations share: the C handle, the per-member
+    results, the train / eval steps and the k-fold loop.  ``_C`` is the prefix of the engine's C
+    entry points (``mpo_pop`` / ``mpo_tc`` / ``mpo_dn``: the same signatures under each)."""
 
-    def __init__(self, specs, batch=100, device=None, init=None, init_seed=0):
-        self.specs = [s if isinstance(s, TrialSpec) else TrialSpec(**s) for s in specs]
-        self.n = len(self.specs)
+    _C = None
+    _val_offset = None      # a method that returns what fit_folds adds to the validation loss
+
+    def _create(self, n, batch, device, head, *tail):
+        """``<_C>_create(head, n, batch, *tail, &handle)``."""
+        self.n = int(n)
         self.batch = int(batch)
         self.device = torch.device(device if device is not None else "cuda")
-        L = lib()
-        arr = (MpoCnnSpec * self.n)()
-        for i, s in enumerate(self.specs):
-            arr[i] = MpoCnnSpec(int(s.nb_filters), int(s.kernel_size), int(s.pool_size), int(s.dense),
-                                float(s.lr), float(s.dropout), int(s.seed) & 0xFFFFFFFF, s.options())
         h = ctypes.c_void_p()
-        check(L.mpo_pop_create(arr, self.n, self.batch, ctypes.byref(h)), "mpo_pop_create")
+        check(getattr(lib(), f"{self._C}_create")(head, self.n, self.batch, *tail, ctypes.byref(h)),
+              f"{self._C}_create")
         self._h = h
-        sz = MpoPopSizes()
-        check(L.mpo_pop_sizes(h, ctypes.byref(sz)), "mpo_pop_sizes")
+
+    def _call(self, name, *args):
+        check(getattr(lib(), f"{self._C}_{name}")(self._h, *args), f"{self._C}_{name}")
+
+    def _enqueue(self, name, *args):
+        """An entry point that takes the stream last, called with the engine's device current."""
+        with torch.cuda.device(self.device):
+            self._call(name, *args, _lib.stream_handle(self.device))
+
+    def _alloc_results(self):
+        self.loss = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+        self.val_loss_sum = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+        self.val_correct = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        self.step_count = 0
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                getattr(lib(), f"{self._C}_destroy")(h)
+            except Exception:
+                pass
+            self._h = None
+
+    def reset_optimizer(self):
+        self.adam_m.zero_()
+        self.adam_v.zero_()
+        self.step_count = 0
+
+    # -- steps --------------------------------------------------------------------
+    def _check(self, x, labels, order, row0):
+        """What an engine refuses before a step reaches the C call (topclass)."""
+
+    def train_step(self, x, labels, order, row0, step=None):
+        """x [n, ...] f32 (the engine's sample shape), labels [n] i32, order [n_members, L] i32 (device)."""
+        self._check(x, labels, order, int(row0))
+        step = self.step_count if step is None else int(step)
+        self._enqueue("train_step", ptr(x), ptr(labels), ptr(order), int(order.shape[1]), int(row0), step,
+                      ptr(self.loss))
+        self.step_count = step + 1
+        return self.loss
+
+    def eval_reset(self):
+        self.val_loss_sum.zero_()
+        self.val_correct.zero_()
+
+    def eval_step(self, x, labels, order, row0):
+        self._check(x, labels, order, int(row0))
+        self._enqueue("eval_step", ptr(x), ptr(labels), ptr(order), int(order.shape[1]), int(row0),
+                      ptr(self.val_loss_sum), ptr(self.val_correct))
+
+    # -- full k-fold training -----------------------------------------------------
+    def fit_folds(self, x, labels, folds, n_fold, epochs, record_train_loss=False, holdout=None, progress=None,
+                  stopping=None, retire_stopped=False):
+        """Train every member for ``epochs`` on its fold's training indices (in
+        order, no shuffle), validating once per epoch (validate_every =
+        count/batch, option3:260).  ``folds[i]`` is member i's fold index;
+        ``progress(epoch, epochs)`` is called after each epoch's validation;
+        ``stopping`` (a :class:`~mpi_opt_amd.stopping.StopRule`) ends members early;
+        ``retire_stopped`` also takes them out of the steps the others still run
+        (:func:`train_folds`: their later entries are NaN; nothing changes on an engine
+        without ``set_active``).  DenseNet's val_loss = mean CE + l2 penalty (Keras).
+        Returns {"val_loss": [n, epochs], "val_acc": [n, epochs], "epochs_run": [n], ...}."""
+        return train_folds(self, x, labels, folds, n_fold, epochs, record_train_loss, holdout, progress, stopping,
+                           val_offset=self._val_offset, retire_stopped=retire_stopped)
+
+
+class _Retirable:
+    """``set_active`` / ``step_work`` of the engines whose C side has them (MNIST, DenseNet)."""
+
+    def set_active(self, mask):
+        """``mpo_*_set_active``: members with a false entry of ``mask`` [n] take no
+        part in the following train / eval steps (no kernel work; their parameters,
+        Adam (and DenseNet's BN) state and ``loss`` / ``val_*`` entries are not written;
+        DenseNet's :meth:`penalty` still covers every member) until a later
+        mask brings them back.  An active member's bits do not change.  Waits for
+        the current stream; not capturable."""
+        m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0)
+        if m.size != self.n:
+            raise ValueError(f"set_active: mask of {m.size} entries for {self.n} members")
+        host = (ctypes.c_uint8 * self.n)(*m.astype(np.uint8).tolist())
+        self._enqueue("set_active", ctypes.cast(host, ctypes.c_void_p))
+        self.active = m.copy()
+
+    def step_work(self):
+        """(workgroups, launches) of one train step under the current mask."""
+        work, launches = ctypes.c_int64(), ctypes.c_int64()
+        self._call("step_work", ctypes.byref(work), ctypes.byref(launches))
+        return int(work.value), int(launches.value)
+
+
+class _FlatArenaPopulation(_PopulationBase):
+    """The MNIST and topclass engines: ragged members in flat arenas, each member's eight
+    ``PARAM_NAMES`` tensors and its ``ACT_NAMES`` activations at offsets the C plan reports."""
+
+    ACT_NAMES = ()
+
+    def _bind(self, init, init_seed):
+        """Layout queries, arenas, ``bind`` and the members' initial parameters."""
+        sz = _lib.MpoPopSizes()
+        self._call("sizes", ctypes.byref(sz))
         self.n_params = int(sz.n_params)
-        self.layout = []
-        offs = (ctypes.c_int64 * 9)()
+        self.layout, self.act_layout = [], []
+        offs = (ctypes.c_int64 * (len(PARAM_NAMES) + 1))()
+        aoffs = (ctypes.c_int64 * len(self.ACT_NAMES))()
         for i in range(self.n):
-            check(L.mpo_pop_param_layout(h, i, offs), "mpo_pop_param_layout")
+            self._call("param_layout", i, offs)
             self.layout.append([int(v) for v in offs])
-        self.act_layout = []
-        aoffs = (ctypes.c_int64 * 15)()
-        for i in range(self.n):
-            check(L.mpo_pop_act_layout(h, i, aoffs), "mpo_pop_act_layout")
-            self.act_layout.append(dict(zip(ACT_NAMES, [int(v) for v in aoffs])))
+            self._call("act_layout", i, aoffs)
+            self.act_layout.append(dict(zip(self.ACT_NAMES, [int(v) for v in aoffs])))
         dev = self.device
         self.params = torch.zeros(self.n_params, dtype=torch.float32, device=dev)
         self.grads = torch.zeros_like(self.params)
@@ -208,40 +304,13 @@ class PopulationEngine:
         self.adam_v = torch.zeros_like(self.params)
         self.act = torch.zeros(int(sz.act_floats), dtype=torch.float32, device=dev)
         self.tables = torch.empty(int(sz.table_bytes), dtype=torch.uint8, device=dev)
-        self.loss = torch.zeros(self.n, dtype=torch.float32, device=dev)
-        self.val_loss_sum = torch.zeros(self.n, dtype=torch.float32, device=dev)
-        self.val_correct = torch.zeros(self.n, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            check(L.mpo_pop_bind(h, ptr(self.params), ptr(self.grads), ptr(self.adam_m), ptr(self.adam_v),
-                                 ptr(self.act), ptr(self.tables), _lib.stream_handle(dev)), "mpo_pop_bind")
+        self._alloc_results()
+        self._enqueue("bind", ptr(self.params), ptr(self.grads), ptr(self.adam_m), ptr(self.adam_v), ptr(self.act),
+                      ptr(self.tables))
         if init is None:
             init = [glorot_uniform_init(s, init_seed + i) for i, s in enumerate(self.specs)]
         for i, p in enumerate(init):
             self.set_params(i, p)
-        self.step_count = 0
-        self.active = np.ones(self.n, dtype=bool)
-
-    # -- retiring members ---------------------------------------------------------
-    def set_active(self, mask):
-        """``mpo_pop_set_active``: members with a false entry of ``mask`` [n] take no
-        part in the following train / eval steps (no kernel work; their parameters,
-        Adam state and ``loss`` / ``val_*`` entries are not written) until a later
-        mask brings them back.  An active member's bits do not change.  Waits for
-        the current stream; not capturable."""
-        self.active = _set_active(self, lib().mpo_pop_set_active, mask)
-
-    def step_work(self):
-        """(workgroups, launches) of one train step under the current mask."""
-        return _step_work(self, lib().mpo_pop_step_work)
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h is not None and h.value:
-            try:
-                lib().mpo_pop_destroy(h)
-            except Exception:
-                pass
-            self._h = None
 
     # -- parameters -------------------------------------------------------------
     def _slices(self, i):
@@ -250,26 +319,45 @@ class PopulationEngine:
         return {n: (o[j], shapes[n]) for j, n in enumerate(PARAM_NAMES)}
 
     def set_params(self, i, params):
-        flat = []
         for n, (off, shape) in self._slices(i).items():
-            a = np.asarray(params[n], dtype=np.float32).reshape(shape)
-            cnt = int(np.prod(shape))
-            self.params[off:off + cnt].copy_(torch.from_numpy(a.reshape(-1)))
-            flat.append(cnt)
+            a = np.ascontiguousarray(np.asarray(params[n], dtype=np.float32).reshape(shape))
+            self.params[off:off + a.size].copy_(torch.from_numpy(a.reshape(-1)))
+
+    def _read(self, arena, i):
+        base, end = self.layout[i][0], self.layout[i][-1]
+        host = arena[base:end].cpu().numpy()
+        return {n: host[off - base:off - base + int(np.prod(shape))].reshape(shape).copy()
+                for n, (off, shape) in self._slices(i).items()}
 
     def get_params(self, i):
-        out = {}
-        host = self.params.cpu().numpy()
-        for n, (off, shape) in self._slices(i).items():
-            cnt = int(np.prod(shape))
-            out[n] = host[off:off + cnt].reshape(shape).copy()
-        return out
+        return self._read(self.params, i)
 
-    def activation(self, i, name, shape):
-        """Copy of member i's activation tensor ``name`` (diagnostics / tests)."""
+    def get_grads(self, i):
+        """Member i's gradients of the last train step (Keras shapes)."""
+        return self._read(self.grads, i)
+
+    def activation(self, i, name, shape, dtype=torch.float32):
+        """Copy of member i's activation tensor ``name`` of the last step (diagnostics /
+        tests), its floats viewed as ``dtype``."""
         off = self.act_layout[i][name]
-        cnt = int(np.prod(shape))
-        return self.act[off:off + cnt].reshape(shape).cpu().numpy()
+        return self.act[off:off + int(np.prod(shape))].view(dtype).reshape(shape).cpu().numpy()
+
+
+class PopulationEngine(_Retirable, _FlatArenaPopulation):
+    """A population of ragged CNN members resident on one GPU."""
+
+    _C = "mpo_pop"
+    ACT_NAMES = ACT_NAMES
+
+    def __init__(self, specs, batch=100, device=None, init=None, init_seed=0):
+        self.specs = [s if isinstance(s, TrialSpec) else TrialSpec(**s) for s in specs]
+        arr = (_lib.MpoCnnSpec * len(self.specs))()
+        for i, s in enumerate(self.specs):
+            arr[i] = _lib.MpoCnnSpec(int(s.nb_filters), int(s.kernel_size), int(s.pool_size), int(s.dense),
+                                     float(s.lr), float(s.dropout), int(s.seed) & 0xFFFFFFFF, s.options())
+        self._create(len(self.specs), batch, device, arr)
+        self._bind(init, init_seed)
+        self.active = np.ones(self.n, dtype=bool)
 
     def argmax_table(self, i):
         """Member i's max-pool argmax (uint8, [batch, s*s*F]) of the last forward."""
@@ -278,22 +366,6 @@ class PopulationEngine:
         n = self.batch * K1
         raw = self.act.view(torch.uint8)[off:off + n]
         return raw.cpu().numpy().reshape(self.batch, K1)
-
-    def reset_optimizer(self):
-        self.adam_m.zero_()
-        self.adam_v.zero_()
-        self.step_count = 0
-
-    # -- steps --------------------------------------------------------------------
-    def train_step(self, x, labels, order, row0, step=None):
-        """x [n,784] f32, labels [n] i32, order [n_members, L] i32 (device)."""
-        step = self.step_count if step is None else int(step)
-        with torch.cuda.device(self.device):
-            check(lib().mpo_pop_train_step(self._h, ptr(x), ptr(labels), ptr(order), int(order.shape[1]), int(row0),
-                                           step, ptr(self.loss), _lib.stream_handle(self.device)),
-                  "mpo_pop_train_step")
-        self.step_count = step + 1
-        return self.loss
 
     def profile(self, reset=True):
         """Per-phase device ms since the last reset ({phase: ms}); empty unless the
@@ -307,47 +379,6 @@ class PopulationEngine:
             name, ms = line.split()
             out[name] = float(ms)
         return out
-
-    def eval_reset(self):
-        self.val_loss_sum.zero_()
-        self.val_correct.zero_()
-
-    def eval_step(self, x, labels, order, row0):
-        with torch.cuda.device(self.device):
-            check(lib().mpo_pop_eval_step(self._h, ptr(x), ptr(labels), ptr(order), int(order.shape[1]), int(row0),
-                                          ptr(self.val_loss_sum), ptr(self.val_correct),
-                                          _lib.stream_handle(self.device)), "mpo_pop_eval_step")
-
-    # -- full k-fold training -----------------------------------------------------
-    def fit_folds(self, x, labels, folds, n_fold, epochs, record_train_loss=False, holdout=None, progress=None,
-                  stopping=None, retire_stopped=False):
-        """Train every member for ``epochs`` on its fold's training indices (in
-        order, no shuffle), validating once per epoch (validate_every =
-        count/batch, option3:260).  ``folds[i]`` is member i's fold index;
-        ``progress(epoch, epochs)`` is called after each epoch's validation;
-        ``stopping`` (a :class:`~mpi_opt_amd.stopping.StopRule`) ends members early;
-        ``retire_stopped`` also takes them out of the steps the others still run
-        (:func:`train_folds`: their later entries are NaN).
-        Returns {"val_loss": [n, epochs], "val_acc": [n, epochs], "epochs_run": [n], ...}."""
-        return train_folds(self, x, labels, folds, n_fold, epochs, record_train_loss, holdout, progress, stopping,
-                           retire_stopped=retire_stopped)
-
-
-def _set_active(eng, fn, mask):
-    """Shared by the two engines' ``set_active``: the mask as the C call's host bytes."""
-    m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0)
-    if m.size != eng.n:
-        raise ValueError(f"set_active: mask of {m.size} entries for {eng.n} members")
-    host = (ctypes.c_uint8 * eng.n)(*m.astype(np.uint8).tolist())
-    with torch.cuda.device(eng.device):
-        check(fn(eng._h, ctypes.cast(host, ctypes.c_void_p), _lib.stream_handle(eng.device)), fn.__name__)
-    return m.copy()
-
-
-def _step_work(eng, fn):
-    work, launches = ctypes.c_int64(), ctypes.c_int64()
-    check(fn(eng._h, ctypes.byref(work), ctypes.byref(launches)), fn.__name__)
-    return int(work.value), int(launches.value)
 
 
 def train_folds(eng, x, labels, folds, n_fold, epochs, record_train_loss=False, holdout=None, progress=None,
