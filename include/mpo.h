@@ -664,6 +664,39 @@ typedef struct MpoDimDesc {
 int mpo_space_sample(const MpoDimDesc* dims, int n_dims, int d, uint64_t seed, int64_t first, int64_t m,
                      double* out, void* stream);
 
+/* Candidates that ARE the legal points of the discrete dimensions (opt-in:
+ * Optimizer(candidates="lattice")).  skopt scores random draws of a relaxed box, polishes
+ * them in that box and rounds the result; here every combination of the Integer and
+ * Categorical values is a candidate and only the Reals are drawn.  NOT the reference's
+ * semantics, and not its stream.
+ * The law (fixed: tests compare bits with a numpy restatement, tests/test_lattice_gpu.py):
+ *   Discrete dimensions are the Integers and the Categoricals.  The radix of an Integer of
+ *   span s = count is s + 1, that of a Categorical its count c.  L is the product of the
+ *   radices, 1 for a space without a discrete dimension; L > 2^62 is MPO_EINVAL from both
+ *   calls.
+ *   Row r (first <= r < first + m) belongs to lattice point l = r mod L.  l is a mixed-radix
+ *   number over the discrete dimensions in table order with the LAST one fastest
+ *   (itertools.product over their values): digit_j = (l / place_j) mod radix_j, place_j the
+ *   product of the radices of the discrete dimensions after j.
+ *   Integer, digit k      0.0 when s == 0, else (double)k / (double)s: the grid of
+ *                         Integer.transform
+ *   Categorical, digit j  one column: (double)j; else the one-hot row of j (the widths of
+ *                         mpo_space_sample)
+ *   Real                  exactly the column mpo_space_sample(seed) writes at row r: the
+ *                         Philox counter (r low 32, r high 32, b, 0) of its pair b, its half
+ *                         of the output words and u53.  Rows of one lattice point (r, r + L,
+ *                         ...) so carry different Reals.
+ * Rows and l are 64-bit; with L < 2^32 the digits are taken in 32-bit arithmetic, the same
+ * integers.
+ * mpo_space_lattice_size is host only: *L from a checked table (no d: it writes no rows).
+ * mpo_space_lattice takes mpo_space_sample's arguments with its conventions and refusals:
+ * dims is a HOST array that reaches the kernel by value; every argument is validated before
+ * any GPU call; m == 0 returns MPO_OK and launches nothing; only enqueues on `stream`: no
+ * workspace, no allocation, no synchronisation, capturable. */
+int mpo_space_lattice_size(const MpoDimDesc* dims, int n_dims, int64_t* L);
+int mpo_space_lattice(const MpoDimDesc* dims, int n_dims, int d, uint64_t seed, int64_t first, int64_t m,
+                      double* out, void* stream);
+
 /* ------------------------------------------------------------------------
  * L-BFGS-B drivers (host C++, no Python in the loop).  skopt's refit runs
  * scipy.optimize.minimize(method="L-BFGS-B") from sklearn's
@@ -695,6 +728,15 @@ int mpo_lbfgsb_batched(int nvar, int nruns, const double* x0, const double* boun
                        mpo_fg_batch_fn fg, void* user, double* x_out, double* f_out, int32_t* stats,
                        int32_t* rounds);
 
+/* mpo_lbfgsb_batched with a column mask shared by all runs: frozen [nvar], and where
+ * frozen[j] != 0 run r holds coordinate j at its start -- its bounds there are
+ * lo = hi = x0[r][j], clipped into bounds[j] first as every start is; L-BFGS-B treats such a
+ * variable as fixed (scipy's does under the same bounds), so x_out[r][j] is that value bit
+ * for bit.  A null mask is mpo_lbfgsb_batched. */
+int mpo_lbfgsb_batched_frozen(int nvar, int nruns, const double* x0, const double* bounds, const uint8_t* frozen,
+                              const MpoLbfgsbOptions* opts, mpo_fg_batch_fn fg, void* user, double* x_out,
+                              double* f_out, int32_t* stats, int32_t* rounds);
+
 /* A rendezvous for the concurrent refits on one device (the cl_min chains):
  * fits that share it evaluate their pending rounds together, one grouped launch
  * set per round of all registered fits, each theta's result unchanged.  Thread
@@ -724,6 +766,17 @@ int mpo_gp_polish_host(const MpoGpModel* model, const double* starts, const int3
                        const double* bounds, const MpoLbfgsbOptions* opts, double y_opt, double xi, double kappa,
                        double* x_host, int32_t* acq_host, double* f_host, double* g_host, double* x_out,
                        double* f_out, int32_t* stats, int32_t* rounds, void* stream);
+
+/* mpo_gp_polish_host that moves the continuous columns only (NOT the reference's semantics;
+ * the polish of Optimizer(candidates="lattice")): frozen [d] as in mpo_lbfgsb_batched_frozen,
+ * so the Integer and Categorical columns of every start stay where the lattice put them.  A
+ * null mask is mpo_gp_polish_host.  The cost-aware, committee and pathwise polishes have no
+ * such variant. */
+int mpo_gp_polish_frozen_host(const MpoGpModel* model, const double* starts, const int32_t* acq, int nruns,
+                              const double* bounds, const uint8_t* frozen, const MpoLbfgsbOptions* opts,
+                              double y_opt, double xi, double kappa, double* x_host, int32_t* acq_host,
+                              double* f_host, double* g_host, double* x_out, double* f_out, int32_t* stats,
+                              int32_t* rounds, void* stream);
 
 /* mpo_gp_polish_host on the cost-aware objective: L-BFGS-B from starts [nruns][d] on
  * acquisition acq[r] (MPO_ACQ_EI / MPO_ACQ_PI) per unit cost, one mpo_gp_acq_ps_grad_host

@@ -167,8 +167,12 @@ SIGNATURES = {
     "mpo_gp_paths_grad": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpPaths), _P, _P, _I, _P, _P, _P]),
     "mpo_gp_paths_grad_host": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpPaths), _P, _P, _I, _P, _P, _P]),
     "mpo_space_sample": (_I, [ctypes.POINTER(MpoDimDesc), _I, _I, ctypes.c_uint64, _I64, _I64, _P, _P]),
+    "mpo_space_lattice_size": (_I, [ctypes.POINTER(MpoDimDesc), _I, ctypes.POINTER(ctypes.c_int64)]),
+    "mpo_space_lattice": (_I, [ctypes.POINTER(MpoDimDesc), _I, _I, ctypes.c_uint64, _I64, _I64, _P, _P]),
     "mpo_lbfgsb_batched": (_I, [_I, _I, _P, _P, ctypes.POINTER(MpoLbfgsbOptions), FG_BATCH_FN, _P, _P, _P, _P,
                                 _P]),
+    "mpo_lbfgsb_batched_frozen": (_I, [_I, _I, _P, _P, _P, ctypes.POINTER(MpoLbfgsbOptions), FG_BATCH_FN, _P, _P, _P,
+                                       _P, _P]),
     "mpo_gp_lml_batcher_create": (_I, [_I, ctypes.POINTER(ctypes.c_void_p)]),
     "mpo_gp_lml_batcher_destroy": (_I, [_P]),
     "mpo_gp_lml_batcher_stats": (_I, [_P, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
@@ -176,6 +180,9 @@ SIGNATURES = {
                                  _SZ, _P, _P, _P, _P, _P, _P]),
     "mpo_gp_polish_host": (_I, [ctypes.POINTER(MpoGpModel), _P, _P, _I, _P, ctypes.POINTER(MpoLbfgsbOptions), _D,
                                 _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mpo_gp_polish_frozen_host": (_I, [ctypes.POINTER(MpoGpModel), _P, _P, _I, _P, _P,
+                                       ctypes.POINTER(MpoLbfgsbOptions), _D, _D, _D, _P, _P, _P, _P, _P, _P, _P, _P,
+                                       _P]),
     "mpo_gp_polish_ps_host": (_I, [ctypes.POINTER(MpoGpModel), ctypes.POINTER(MpoGpModel), _P, _P, _I, _P,
                                    ctypes.POINTER(MpoLbfgsbOptions), _D, _D, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mpo_gp_polish_committee_host": (_I, [_P, _I, _P, _P, _I, _P, ctypes.POINTER(MpoLbfgsbOptions), _D, _D, _D, _P, _P,

@@ -1,5 +1,6 @@
-"""Acquisition candidates drawn on the device (``mpo_space_sample``), the opt-in
-``Optimizer(candidates="device")`` source.
+"""Acquisition candidates written on the device: the opt-in ``Optimizer(candidates="device")``
+source (``mpo_space_sample``, below) and the ``"lattice"`` source (``mpo_space_lattice``, at
+the end of this docstring).
 
 skopt draws the ``n_points`` candidates of every ask on the host, one column at a
 time from the optimizer's RandomState (``Space.rvs_transformed``), and the result is
@@ -18,14 +19,29 @@ same grid ``k / (high - low)`` that ``Integer.transform`` produces; categories a
 "The host path" is this package's ``space.py``: like it, this source does not honour a
 ``prior`` given to an ``Integer`` (log-uniform) or a ``Categorical`` (category weights),
 which skopt's own ``rvs`` would; a Real's prior only warps its transformed interval.
+
+``"lattice"`` is NOT skopt's semantics either, and departs further.  skopt treats Integer and
+Categorical dimensions as a continuous box: it scores random draws, polishes the best in the
+relaxed unit cube and rounds the result, so the acquisition value that picked a point is not
+the value at the point that gets trained.  Here the candidate set IS the legal set: row ``r``
+is lattice point ``r mod L`` of the ``L`` combinations of the discrete values
+(``itertools.product`` order, the last discrete dimension fastest) and its Real columns are
+the ones ``mpo_space_sample(seed)`` writes at row ``r`` (the law is in include/mpo.h); the
+polish then moves the Real columns only (:func:`frozen_columns`).  No ``prior`` of an Integer
+or a Categorical is honoured, as above.
 """
 from __future__ import annotations
+
+import ctypes
+
+import numpy as np
 
 from . import _lib
 from .space import Categorical, Integer, Space
 
-#: Optimizer(candidates=...): skopt's host stream, or the device law of this module
-SOURCES = ("host", "device")
+#: Optimizer(candidates=...): skopt's host stream, the device law of this module, or every
+#: legal point of the discrete dimensions (neither of the last two is skopt's)
+SOURCES = ("host", "device", "lattice")
 
 
 def dim_table(space):
@@ -61,3 +77,41 @@ def sample_transformed(space, n, seed, device=None, first=0):
         _lib.check(_lib.lib().mpo_space_sample(table, len(table), d, int(seed), int(first), int(n), _lib.ptr(out),
                                                _lib.stream_handle(dev)), "mpo_space_sample")
     return out
+
+
+def lattice_size(space):
+    """``L``, the number of combinations of the Integer and Categorical values of ``space``
+    (``mpo_space_lattice_size``; 1 without such a dimension).  Host only.  Raises
+    :class:`~mpi_opt_amd._lib.MpoError` past 2^62."""
+    table, _ = dim_table(space)
+    L = ctypes.c_int64(0)
+    _lib.check(_lib.lib().mpo_space_lattice_size(table, len(table), ctypes.byref(L)), "mpo_space_lattice_size")
+    return int(L.value)
+
+
+def lattice_transformed(space, n, seed, device=None, first=0):
+    """Rows ``first .. first + n - 1`` of the lattice candidates of ``seed`` in the transformed
+    space, an ``(n, d)`` float64 tensor on ``device`` enqueued on the current torch stream (no
+    synchronisation): row ``r`` holds lattice point ``r mod L`` in its discrete columns and the
+    Reals of ``sample_transformed(space, ., seed)``'s row ``r``.  NOT skopt's semantics (see the
+    module docstring)."""
+    import torch
+
+    from .gp import _dev
+
+    table, d = dim_table(space)
+    dev = _dev(device)
+    out = torch.empty((int(n), d), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().mpo_space_lattice(table, len(table), d, int(seed), int(first), int(n), _lib.ptr(out),
+                                                _lib.stream_handle(dev)), "mpo_space_lattice")
+    return out
+
+
+def frozen_columns(space):
+    """Bool mask over the transformed columns of ``space``: True for the column of an Integer
+    and every column of a Categorical -- the columns a lattice candidate fixes and the polish
+    must not move."""
+    dims = space.dimensions if isinstance(space, Space) else Space(space).dimensions
+    return np.array([isinstance(dim, (Integer, Categorical)) for dim in dims for _ in range(dim.transformed_size)],
+                    dtype=bool)

@@ -1016,19 +1016,37 @@ struct Options {
 // evaluates the point each live run needs in one fg(batch, X, ids, f, g) call.
 // Outputs: x_out [nruns][nvar], f_out [nruns] (the last value delivered to the run,
 // scipy's OptimizeResult.fun), stats [nruns][4] = (nit, nfev, status, 0).
+// With a mask frozen [nvar] (or null), run r keeps every coordinate j with frozen[j] != 0 at
+// its clipped start: its bounds there are lo = hi = clip(x0[r][j]), a fixed variable of
+// L-BFGS-B (as scipy's is under such bounds), so those runs get a bounds table each.
 template <class FG>
 int drive(int nvar, int nruns, const double* x0, const double* bounds, const Options& o, FG&& fg, double* x_out,
-          double* f_out, int32_t* stats, int32_t* rounds_out) {
-    std::vector<double> lo(nvar), hi(nvar);
+          double* f_out, int32_t* stats, int32_t* rounds_out, const uint8_t* frozen = nullptr) {
+    std::vector<double> lo(nvar), hi(nvar), lo_run, hi_run;
     std::vector<int> nbd(nvar, 2);
     for (int i = 0; i < nvar; ++i) { lo[i] = bounds[2 * i]; hi[i] = bounds[2 * i + 1]; }
+    if (frozen) {
+        lo_run.resize((size_t)nruns * nvar);
+        hi_run.resize((size_t)nruns * nvar);
+    }
     const double factr = o.ftol / 2.220446049250313e-16;
     std::vector<Lbfgsb> runs;
     runs.reserve(nruns);
     std::vector<double> xs(nvar);
     for (int r = 0; r < nruns; ++r) {
-        runs.emplace_back(nvar, lo.data(), hi.data(), nbd.data(), factr, o.gtol, o.maxcor, o.maxls, o.maxiter, o.maxfun);
         for (int i = 0; i < nvar; ++i) xs[i] = std::min(std::max(x0[(size_t)r * nvar + i], lo[i]), hi[i]);
+        const double *lo_r = lo.data(), *hi_r = hi.data();
+        if (frozen) {
+            double* l = &lo_run[(size_t)r * nvar];
+            double* h = &hi_run[(size_t)r * nvar];
+            for (int i = 0; i < nvar; ++i) {
+                l[i] = frozen[i] ? xs[i] : lo[i];
+                h[i] = frozen[i] ? xs[i] : hi[i];
+            }
+            lo_r = l;
+            hi_r = h;
+        }
+        runs.emplace_back(nvar, lo_r, hi_r, nbd.data(), factr, o.gtol, o.maxcor, o.maxls, o.maxiter, o.maxfun);
         runs.back().start(xs.data());
     }
     std::vector<int32_t> live(nruns), next;
@@ -1096,7 +1114,8 @@ Options to_options(const MpoLbfgsbOptions* o) {
 template <class Objective>
 int polish_drive(int d, int nruns, const double* starts, const double* bounds, const MpoLbfgsbOptions* opts,
                  const int32_t* ids_src, double* x_host, int32_t* id_host, double* f_host, double* g_host,
-                 double* x_out, double* f_out, int32_t* stats, int32_t* rounds, Objective&& objective) {
+                 double* x_out, double* f_out, int32_t* stats, int32_t* rounds, Objective&& objective,
+                 const uint8_t* frozen = nullptr) {
     auto eval = [&](int b, const double* Xp, const int32_t* ids, double* f, double* g) -> int {
         std::memcpy(x_host, Xp, sizeof(double) * (size_t)b * d);
         for (int i = 0; i < b; ++i) id_host[i] = ids_src[ids[i]];
@@ -1106,7 +1125,7 @@ int polish_drive(int d, int nruns, const double* starts, const double* bounds, c
         std::memcpy(g, g_host, sizeof(double) * (size_t)b * d);
         return 0;
     };
-    return drive(d, nruns, starts, bounds, to_options(opts), eval, x_out, f_out, stats, rounds);
+    return drive(d, nruns, starts, bounds, to_options(opts), eval, x_out, f_out, stats, rounds, frozen);
 }
 
 // Rendezvous of the concurrent refits on one device (the cl_min chains' worker
@@ -1238,9 +1257,9 @@ int mpo_gp_lml_batcher_stats(const void* handle, int64_t* launches, int64_t* rou
     return MPO_OK;
 }
 
-int mpo_lbfgsb_batched(int nvar, int nruns, const double* x0, const double* bounds, const MpoLbfgsbOptions* opts,
-                       mpo_fg_batch_fn fg, void* user, double* x_out, double* f_out, int32_t* stats,
-                       int32_t* rounds) {
+int mpo_lbfgsb_batched_frozen(int nvar, int nruns, const double* x0, const double* bounds, const uint8_t* frozen,
+                              const MpoLbfgsbOptions* opts, mpo_fg_batch_fn fg, void* user, double* x_out,
+                              double* f_out, int32_t* stats, int32_t* rounds) {
     MPO_GUARD_BEGIN
     MPO_CHECK_ARG(options_ok(nvar, nruns, x0, bounds, opts) && fg && x_out && f_out,
                   "mpo_lbfgsb_batched: bad arguments (nvar=%d nruns=%d)", nvar, nruns);
@@ -1249,8 +1268,14 @@ int mpo_lbfgsb_batched(int nvar, int nruns, const double* x0, const double* boun
         if (rc != 0) mpo::set_error("mpo_lbfgsb_batched: objective callback returned %d", rc);
         return rc != 0 ? MPO_EINVAL : 0;
     };
-    return drive(nvar, nruns, x0, bounds, to_options(opts), eval, x_out, f_out, stats, rounds);
+    return drive(nvar, nruns, x0, bounds, to_options(opts), eval, x_out, f_out, stats, rounds, frozen);
     MPO_GUARD_END
+}
+
+int mpo_lbfgsb_batched(int nvar, int nruns, const double* x0, const double* bounds, const MpoLbfgsbOptions* opts,
+                       mpo_fg_batch_fn fg, void* user, double* x_out, double* f_out, int32_t* stats,
+                       int32_t* rounds) {
+    return mpo_lbfgsb_batched_frozen(nvar, nruns, x0, bounds, nullptr, opts, fg, user, x_out, f_out, stats, rounds);
 }
 
 int mpo_gp_fit_lml_host(const double* X, const double* y_norm, int n, int d, const double* starts, int nruns,
@@ -1318,10 +1343,11 @@ int mpo_gp_fit_lml_host(const double* X, const double* y_norm, int n, int d, con
     MPO_GUARD_END
 }
 
-int mpo_gp_polish_host(const MpoGpModel* model, const double* starts, const int32_t* acq, int nruns,
-                       const double* bounds, const MpoLbfgsbOptions* opts, double y_opt, double xi, double kappa,
-                       double* x_host, int32_t* acq_host, double* f_host, double* g_host, double* x_out,
-                       double* f_out, int32_t* stats, int32_t* rounds, void* stream) {
+int mpo_gp_polish_frozen_host(const MpoGpModel* model, const double* starts, const int32_t* acq, int nruns,
+                              const double* bounds, const uint8_t* frozen, const MpoLbfgsbOptions* opts,
+                              double y_opt, double xi, double kappa, double* x_host, int32_t* acq_host,
+                              double* f_host, double* g_host, double* x_out, double* f_out, int32_t* stats,
+                              int32_t* rounds, void* stream) {
     MPO_GUARD_BEGIN
     MPO_CHECK_ARG(model && acq && x_host && acq_host && f_host && g_host && x_out && f_out,
                   "mpo_gp_polish_host: null pointer");
@@ -1329,8 +1355,16 @@ int mpo_gp_polish_host(const MpoGpModel* model, const double* starts, const int3
     return polish_drive(model->d, nruns, starts, bounds, opts, acq, x_host, acq_host, f_host, g_host, x_out, f_out,
                         stats, rounds, [&](int b) {
         return mpo_gp_acq_grad_host(model, x_host, b, acq_host, y_opt, xi, kappa, f_host, g_host, stream);
-    });
+    }, frozen);
     MPO_GUARD_END
+}
+
+int mpo_gp_polish_host(const MpoGpModel* model, const double* starts, const int32_t* acq, int nruns,
+                       const double* bounds, const MpoLbfgsbOptions* opts, double y_opt, double xi, double kappa,
+                       double* x_host, int32_t* acq_host, double* f_host, double* g_host, double* x_out,
+                       double* f_out, int32_t* stats, int32_t* rounds, void* stream) {
+    return mpo_gp_polish_frozen_host(model, starts, acq, nruns, bounds, nullptr, opts, y_opt, xi, kappa, x_host,
+                                     acq_host, f_host, g_host, x_out, f_out, stats, rounds, stream);
 }
 
 int mpo_gp_polish_ps_host(const MpoGpModel* fmodel, const MpoGpModel* tmodel, const double* starts,

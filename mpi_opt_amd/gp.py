@@ -274,15 +274,24 @@ class DeviceGP:
             check(rc, "mpo_gp_acq_grad_host")
         return r.fg(B)
 
-    def polish(self, starts, acq_codes, y_opt, xi, kappa, bounds, ftol, maxiter=20, gtol=1e-5, maxfun=15000):
+    def polish(self, starts, acq_codes, y_opt, xi, kappa, bounds, ftol, maxiter=20, gtol=1e-5, maxfun=15000,
+               frozen=None):
         """skopt's polish of its best candidates, whole, in ``mpo_gp_polish_host``:
         L-BFGS-B (libmpo.so's host driver) from each row of ``starts`` (B, d) on
         acquisition ``acq_codes[r]``, one ``mpo_gp_acq_grad_host`` round per
-        iteration of all live runs.  Returns [(x, f)] per run."""
+        iteration of all live runs.  With ``frozen``, a (d,) bool mask (NOT skopt's
+        semantics; ``candidates.frozen_columns``), ``mpo_gp_polish_frozen_host``: every run keeps
+        its start's value in the masked columns.  Returns [(x, f)] per run."""
         starts = _polish_starts(starts, self.d)
-        x, f, _, _ = _run_polish("mpo_gp_polish_host", (ctypes.byref(self.model),),
+        symbol = "mpo_gp_polish_host"
+        if frozen is not None:
+            frozen = np.ascontiguousarray(np.asarray(frozen, dtype=bool).astype(np.uint8))
+            if frozen.shape != (self.d,):
+                raise ValueError(f"frozen must be a ({self.d},) mask, got shape {frozen.shape}")
+            symbol = "mpo_gp_polish_frozen_host"
+        x, f, _, _ = _run_polish(symbol, (ctypes.byref(self.model),),
                                  (float(y_opt), float(xi), float(kappa)), starts, acq_codes, bounds, ftol, maxiter,
-                                 gtol, maxfun, self._ensure_ag(len(starts)), self._ag_stream)
+                                 gtol, maxfun, self._ensure_ag(len(starts)), self._ag_stream, frozen=frozen)
         return [(x[r], float(f[r])) for r in range(len(starts))]
 
     # -- joint posterior -------------------------------------------------------
@@ -645,10 +654,12 @@ def _polish_starts(starts, d):
     return starts
 
 
-def _run_polish(symbol, head_args, tail_args, starts, ids, bounds, ftol, maxiter, gtol, maxfun, round, stream):
+def _run_polish(symbol, head_args, tail_args, starts, ids, bounds, ftol, maxiter, gtol, maxfun, round, stream,
+                frozen=None):
     """One of libmpo.so's polish entry points, ``symbol(*head_args, starts, ids, B, bounds,
     options, *tail_args, round's x / ids / f / g, outputs, stream)``: L-BFGS-B from each row
-    of ``starts`` (B, d) on the objective ``ids[r]`` names.  Returns numpy ``(x (B, d), f (B,),
+    of ``starts`` (B, d) on the objective ``ids[r]`` names.  ``frozen`` (a (d,) uint8 mask, for
+    an entry point that takes one) follows ``bounds``.  Returns numpy ``(x (B, d), f (B,),
     stats (B, 4) = (nit, nfev, status, 0), rounds)``."""
     B, d = starts.shape
     ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
@@ -658,8 +669,9 @@ def _run_polish(symbol, head_args, tail_args, starts, ids, bounds, ftol, maxiter
     f = np.empty(B)
     stats = np.empty((B, 4), np.int32)
     rounds = ctypes.c_int32(0)
-    rc = getattr(lib(), symbol)(*head_args, starts.ctypes.data, ids.ctypes.data, B, b.ctypes.data, ctypes.byref(opts),
-                                *tail_args, *round.ensure(B).ptrs, x.ctypes.data, f.ctypes.data, stats.ctypes.data,
+    mask = () if frozen is None else (frozen.ctypes.data,)
+    rc = getattr(lib(), symbol)(*head_args, starts.ctypes.data, ids.ctypes.data, B, b.ctypes.data, *mask,
+                                ctypes.byref(opts), *tail_args, *round.ensure(B).ptrs, x.ctypes.data, f.ctypes.data, stats.ctypes.data,
                                 ctypes.byref(rounds), stream)
     if rc != 0:
         check(rc, symbol)

@@ -354,7 +354,7 @@ def sample_with_ladder(dev, cand, z, want_samples=True):
         f"(device Cholesky failed at column {out['info'] - 1})")
 
 
-def polish_lockstep(model, starts, acqs, y_opt, xi, kappa, bounds, maxiter=20, driver="native"):
+def polish_lockstep(model, starts, acqs, y_opt, xi, kappa, bounds, maxiter=20, driver="native", frozen=None):
     """skopt's acquisition polish: ``fmin_l_bfgs_b(gaussian_acquisition_1D, x0,
     bounds, approx_grad=False, maxiter=20)`` from every start ``starts[w]`` of
     acquisition ``acqs[w]``.  The runs are independent; they step in lockstep so
@@ -364,13 +364,18 @@ def polish_lockstep(model, starts, acqs, y_opt, xi, kappa, bounds, maxiter=20, d
     Python.  A :class:`PsModel` with "EIps" / "PIps" runs takes the cost-aware objective
     (``mpo_gp_polish_ps_host`` / ``mpo_gp_acq_ps_grad_host``; ``kappa`` unused); a
     :class:`CommitteeModel` the committee's (``mpo_gp_polish_committee_host`` /
-    ``mpo_gp_committee_grad_host``).
+    ``mpo_gp_committee_grad_host``).  ``frozen`` (a bool mask over the columns, the
+    "lattice" candidate source; NOT skopt's semantics): the masked columns of every run stay
+    at its start (``mpo_gp_polish_frozen_host``), for the native driver on one exact GP only.
     Returns [(x, f)] per run."""
     from .gp_fit import FMIN_FTOL, _Lockstep, _setulb, lbfgsb_batched
 
     codes = np.array([acq_code(a) for a in acqs], dtype=np.int32)
     ps = isinstance(model, PsModel)
     com = isinstance(model, CommitteeModel)
+    if frozen is not None and (ps or com or driver != "native"):
+        raise ValueError("a polish with frozen columns runs in the native driver on one exact GP: the cost-aware, "
+                         "committee and scipy-driven polishes have no frozen variant")
     if ps:
         from .gp import acq_grad_ps, polish_ps
 
@@ -383,7 +388,8 @@ def polish_lockstep(model, starts, acqs, y_opt, xi, kappa, bounds, maxiter=20, d
                                     maxiter=maxiter)
         if ps:
             return polish_ps(fdev, tdev, np.array(starts), codes, y_opt, xi, bounds, ftol=FMIN_FTOL, maxiter=maxiter)
-        return model.dev.polish(np.array(starts), codes, y_opt, xi, kappa, bounds, ftol=FMIN_FTOL, maxiter=maxiter)
+        return model.dev.polish(np.array(starts), codes, y_opt, xi, kappa, bounds, ftol=FMIN_FTOL, maxiter=maxiter,
+                                frozen=frozen)
     if driver != "scipy":
         raise ValueError(f"driver {driver!r}: 'native' or 'scipy'")
 
@@ -542,8 +548,12 @@ STRATEGIES = ("cl_min", "cl_mean", "cl_max", "thompson")
 #: (skopt) or for none of them
 LIE_REFIT = ("every", "never")
 #: Optimizer(candidates=...): where the acquisition candidates of a proposal are drawn
-#: (mpi_opt_amd.candidates): "host" is skopt's RandomState stream, "device" is not
-CANDIDATES = ("host", "device")
+#: (mpi_opt_amd.candidates): "host" is skopt's RandomState stream, "device" is not, and
+#: "lattice" (every legal point of the discrete dimensions) is not skopt's semantics at all
+CANDIDATES = ("host", "device", "lattice")
+#: acq_optimizer_kwargs["lattice_max"]: the most rows the "lattice" source writes per proposal
+#: (at d = 32 that is 1 GiB of candidates)
+LATTICE_MAX = 1 << 22
 
 #: the most observations one GP takes (the refit's and the scoring kernels' bound in libmpo.so)
 MAX_GP_POINTS = 2048
@@ -986,6 +996,22 @@ class Optimizer:
     measure zero (Reals exclude the upper bound and skip the host's
     inverse_transform / transform round trip of a few ulp).
 
+    ``candidates="lattice"`` (an addition of this build; NOT skopt's semantics, and nothing is
+    known about its effect on search quality): skopt relaxes Integer and Categorical
+    dimensions to a box, polishes there and rounds, so the acquisition value that picked a
+    point is not the value at the point that gets trained.  Here the candidates ARE the legal
+    points: with L the number of combinations of the discrete values, a proposal draws ONE
+    seed (as "device" does, whatever the space) and scores ``L * max(1, ceil(n_points / L))``
+    rows, row r the lattice point r mod L with the Reals of "device"'s row r
+    (``mpo_space_lattice``, :mod:`~mpi_opt_amd.candidates`).  The "lbfgs" polish moves the
+    Real columns only (``mpo_gp_polish_frozen_host``); on a space without a Real there is
+    nothing to polish and the best candidate of each acquisition is taken, as "sampling"
+    does.  ``acq_optimizer_kwargs["lattice_max"]`` (default 2^22 rows) bounds the set: a space
+    with L above it is refused at construction, nothing is subsampled.  Points already told
+    are not excluded.  Refused together with the "thompson" strategy, "EIps" / "PIps", the
+    "committee" surrogate, and the scipy polish driver on a space with both discrete and Real
+    columns.
+
     ``batch_strategy`` (one of ``STRATEGIES``, an addition of this build): the strategy of
     an ``ask(n)`` that names none; "cl_min" is skopt's default.  "thompson" departs from
     skopt: one fit, one joint draw of n posterior samples over
@@ -1088,6 +1114,8 @@ class Optimizer:
         self._initial_point_generator = initial_point_generator
         self._initial_samples = None
         self.model_queue_size = model_queue_size
+        if candidates == "lattice":
+            self._check_lattice()
         self.device = device
         self.scorer = scorer
         self.cand_acq_funcs_ = ["EI", "LCB", "PI"] if acq_func == "gp_hedge" else [acq_func]
@@ -1102,6 +1130,31 @@ class Optimizer:
         # optional: runs ask(n) batches asynchronously (mpi_opt_amd.chains); ask then
         # returns a LazyBatch whose points resolve when first used
         self.chain_executor = chain_executor
+
+    def _check_lattice(self):
+        """The refusals of ``candidates="lattice"`` (NOT the reference's semantics), at
+        construction: what has no lattice form yet, and a lattice past ``lattice_max``."""
+        from .candidates import frozen_columns, lattice_size
+
+        if self.batch_strategy == "thompson":
+            raise ValueError('candidates="lattice" with the "thompson" strategy is not supported: the joint draw '
+                             "takes at most 4096 points and the paths sampler has its own candidate plumbing")
+        if self.acq_func in PS_ACQS:
+            raise ValueError(f'candidates="lattice" with acq_func {self.acq_func!r} is not supported: the cost-aware '
+                             "polish has no variant that holds the discrete columns still")
+        if self.surrogate == "committee":
+            raise ValueError('candidates="lattice" with surrogate="committee" is not supported: the polish of a '
+                             "committee has no variant that holds the discrete columns still")
+        frozen = frozen_columns(self.space)
+        if DRIVER == "scipy" and self.acq_optimizer == "lbfgs" and frozen.any() and not frozen.all():
+            raise ValueError('candidates="lattice" on a space with discrete and Real dimensions needs the native '
+                             "polish driver: the scipy-driven polish cannot hold columns still")
+        lattice_max = self.acq_optimizer_kwargs.get("lattice_max", LATTICE_MAX)
+        L = lattice_size(self.space)
+        if L > lattice_max:
+            raise ValueError(f'candidates="lattice": the space has L = {L} combinations of discrete values, more '
+                             f'than acq_optimizer_kwargs["lattice_max"] = {lattice_max} rows; nothing is '
+                             "subsampled")
 
     def __setstate__(self, d):
         # checkpoints written before these attributes existed resume with their defaults
@@ -1149,6 +1202,8 @@ class Optimizer:
             raise ValueError(f'acq_func {self.acq_func!r} with the "thompson" strategy is not supported')
         if strategy == "thompson" and self.surrogate == "committee":
             raise ValueError('surrogate="committee" with the "thompson" strategy is not supported')
+        if strategy == "thompson" and self.candidates == "lattice":
+            raise ValueError('candidates="lattice" with the "thompson" strategy is not supported')
         if strategy == "thompson" and self.base_estimator_ == "gp":
             # refused here, before the copy's fit (_thompson_step checks again)
             thompson_config(self.acq_optimizer_kwargs, self.n_points, n_points - max(self._n_initial_points, 0))
@@ -1271,8 +1326,19 @@ class Optimizer:
             if self.model_queue_size is not None and len(self.models) > self.model_queue_size:
                 self.models.pop(0)
 
-        cand_seed = None
-        if self.candidates == "device":
+        cand_seed, lattice, frozen = None, None, None
+        if self.candidates == "lattice":
+            # NOT the reference's semantics: every legal point of the discrete dimensions, whole
+            # copies of the lattice up to n_points rows, each row with Reals of its own.  One
+            # draw, where "device" draws it and whatever the space.
+            from .candidates import frozen_columns, lattice_size, lattice_transformed
+
+            cand_seed = int(self.rng.randint(0, np.iinfo(np.int32).max))
+            lattice = lattice_size(self.space)
+            frozen = frozen_columns(self.space)
+            X = lattice_transformed(self.space, lattice * max(1, -(-self.n_points // lattice)), cand_seed,
+                                    device=self.device)
+        elif self.candidates == "device":
             # one draw, so a batch stays a pure function of its ChainJob; the rows never
             # exist on the host (X is a device tensor; only the winners are gathered below)
             from .candidates import sample_transformed
@@ -1284,7 +1350,9 @@ class Optimizer:
         y_opt = float(np.min(self.yi))
         xi = self.acq_func_kwargs.get("xi", 0.01)
         kappa = self.acq_func_kwargs.get("kappa", 1.96)
-        k = 1 if self.acq_optimizer == "sampling" else min(self.n_restarts_optimizer, X.shape[0])
+        # an all-discrete lattice has nothing to polish: its best candidate is the proposal
+        polish = self.acq_optimizer == "lbfgs" and not (frozen is not None and frozen.all())
+        k = min(self.n_restarts_optimizer, X.shape[0]) if polish else 1
         t3 = time.perf_counter()
         top = self._score_topk(est, X, y_opt, xi, kappa, k)
         t4 = time.perf_counter()
@@ -1303,17 +1371,20 @@ class Optimizer:
             cand_row = lambda i: won[int(i)]  # noqa: E731
             if rec is not None:
                 rec["cand_seed"] = cand_seed
+                if lattice is not None:
+                    rec["lattice"] = lattice
         else:
             cand_row = lambda i: X[i]  # noqa: E731
         self.next_xs_ = []
-        if self.acq_optimizer == "lbfgs":
+        if polish:
             runs = [(a, i) for a in self.cand_acq_funcs_ for i in top[a]]
             polished = polish_lockstep(est, [cand_row(i) for _, i in runs], [a for a, _ in runs], y_opt, xi, kappa,
-                                       self.space.transformed_bounds, driver=DRIVER)
+                                       self.space.transformed_bounds, driver=DRIVER,
+                                       frozen=frozen if frozen is not None and frozen.any() else None)
             t_polish = time.perf_counter() - t4
         for acq in self.cand_acq_funcs_:
             idx = top[acq]
-            if self.acq_optimizer == "sampling":
+            if not polish:
                 next_x = cand_row(idx[0])
             else:
                 results = [polished[w] for w, (a, _) in enumerate(runs) if a == acq]

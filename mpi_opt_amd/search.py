@@ -31,6 +31,10 @@ each lie to the posterior (``mpo_gp_append``).
 reference too: the ``--ei-candidates`` acquisition candidates of a proposal are
 written on the GPU from one seed (``mpo_space_sample``, mpi_opt_amd.candidates)
 instead of being drawn from the optimizer's RandomState on the host.
+``--candidate-source lattice`` departs further, and is NOT the reference's semantics:
+the candidates are every combination of the space's Integer and Categorical values
+(``mpo_space_lattice``) and the polish moves the Real dimensions only, so the point
+that is trained is a point that was scored.
 """
 from __future__ import annotations
 
@@ -96,11 +100,16 @@ def make_parser():
                    help="acquisition candidates per ask (skopt n_points); split over the GPUs when distributed, "
                         "except with --candidate-source device, whose candidates are scored on the asking "
                         "rank's GPU and never split")
-    p.add_argument("--candidate-source", default="host", choices=["host", "device"], dest="candidate_source",
+    p.add_argument("--candidate-source", default="host", choices=["host", "device", "lattice"],
+                   dest="candidate_source",
                    help="where the acquisition candidates of an ask are drawn: host (skopt's RandomState "
-                        "stream, copied to the GPU) or device (NOT the reference's stream: one seed per "
+                        "stream, copied to the GPU), device (NOT the reference's stream: one seed per "
                         "proposal, the candidates written on the GPU as a function of (seed, row); for "
-                        "large --ei-candidates; scored on the asking rank's GPU)")
+                        "large --ei-candidates; scored on the asking rank's GPU) or lattice (NOT the "
+                        "reference's semantics: every combination of the Integer and Categorical values is a "
+                        "candidate, whole copies of that set up to --ei-candidates rows with Reals drawn as "
+                        "device draws them, and the polish moves the Reals only; refused past 2^22 "
+                        "combinations; scored on the asking rank's GPU)")
     p.add_argument("--chain-workers", type=int, default=8,
                    help="concurrent cl_min ask batches per GPU (worker threads, one HIP stream each; their "
                         "refit rounds share launches); 0 runs every ask inline, as the reference's "
@@ -326,7 +335,7 @@ def run_search(args, x=None, y=None, log=print, progress=None, on_population=Non
     if args.expert_size != 512:
         opt_kw["expert_size"] = args.expert_size
     if args.candidate_source != "host":
-        opt_kw["candidates"] = args.candidate_source      # device-drawn candidates (not skopt's stream)
+        opt_kw["candidates"] = args.candidate_source      # written on the device (not skopt's stream)
     if args.thompson_sampler != "joint":
         # pathwise Thompson draws over all --ei-candidates (a random-feature prior; not skopt's semantics)
         opt_kw["acq_optimizer_kwargs"]["ts_sampler"] = args.thompson_sampler
